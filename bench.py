@@ -8,7 +8,9 @@ full step = forward + MaskedL1 + zero_grad + backward + SGD(momentum .9, wd 1e-4
 
 One process per GPU; inputs are resident in HBM before the timed region (synthetic batch, SURVEY.md 8d recipe,
 seed = 1234 + 1000*rank).  Timed region: K steps bracketed by barrier + synchronize, max over ranks.  Rank 0
-prints ONE JSON line.  Extra objects:
+prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...);
+`--dump-outputs DIR` also writes what the last timed step returned (loss, prediction, updated parameters) as float32 .npy
+files.  `--full` adds the extra objects, each measured outside the timed region in passes of its own:
   roofline     -- the dominant kernel (largest total time among the conv kernel instantiations) measured with HIP
                   events in an instrumented eager pass on the step's own stream: algorithmic FLOPs per launch /
                   average launch duration.  The default plan ("split", config.arith) computes every fp32 product from six
@@ -159,6 +161,22 @@ def instrumented_pass(ts):
     return agg, fam
 
 
+def dump_outputs(out_dir, loss, pred, params):
+    """--dump-outputs: what the timed path handed its caller after its last step -- the loss, the prediction and the parameters the
+    SGD update left (in model.parameters() order, so independent of the arena layout) -- as float32 .npy files under out_dir.  A tensor
+    above its element cap is written as `<name>_sample.npy`: the elements at fixed, seeded flat indices (a pure function of the
+    element count), so two builds compare output for output.  At most 4 * (2^23 + 2^22) bytes (48 MiB) in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat_params = torch.cat([p.detach().reshape(-1).float() for p in params])
+    for name, t, cap in (("loss", loss, 1), ("pred", pred, 1 << 23), ("params", flat_params, 1 << 22)):
+        flat = t.detach().reshape(-1).float()
+        if flat.numel() > cap:
+            idx = np.unique(np.random.default_rng(1234).integers(0, flat.numel(), cap, dtype=np.int64))
+            flat, name = flat[torch.from_numpy(idx).to(flat.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy().astype(np.float32))
+
+
 def cpu_baseline(arch, batch, height, width):
     """Oracle (CPU restatement of the reference, pinned to it by golden vectors) full SGD steps on this box's host cores, per
     SURVEY.md 8(d): the configuration's own shape (and, for the headline, b=2 as well), warm-up + timed steps, best and median;
@@ -224,7 +242,7 @@ def eager_loop(model, x, t, warmup, steps, lr=0.01, momentum=0.9, weight_decay=1
     model.train()
     crit = MaskedL1Loss()
     opt = torch.optim.SGD(model.parameters(), lr, momentum=momentum, weight_decay=weight_decay)
-    loss = None
+    loss = pred = None
 
     def one():
         pred = model(x)
@@ -232,19 +250,19 @@ def eager_loop(model, x, t, warmup, steps, lr=0.01, momentum=0.9, weight_decay=1
         opt.zero_grad()
         loss.backward()
         opt.step()
-        return loss
+        return loss, pred
     for _ in range(warmup):
-        loss = one()
+        loss, pred = one()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     host = 0.0
     for _ in range(steps):
         h0 = time.perf_counter()
-        loss = one()
+        loss, pred = one()
         host += time.perf_counter() - h0
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return dt, float(loss.item()), host
+    return dt, float(loss.item()), host, (loss, pred)
 
 
 class PowerReader:
@@ -457,9 +475,11 @@ def dry_run(args, world, rank):
         raise SystemExit("dry run: the bucketed exchange did not produce the all-rank sum over the whole arena")
 
 
-def eager_block(model, x, t, args, operands, fused_value=None):
+def eager_block(model, x, t, args, operands, fused_value=None, dump_dir=None):
     model.operands = operands
-    dt, final_loss, host = eager_loop(model, x, t, args.warmup, args.steps)
+    dt, final_loss, host, (loss, pred) = eager_loop(model, x, t, args.warmup, args.steps)
+    if dump_dir:
+        dump_outputs(dump_dir, loss, pred, model.parameters())
     v = args.batch * args.steps / dt
     blk = {"operands": operands, "value": round(v, 2), "unit": "samples/s", "ms_per_step": round(1e3 * dt / args.steps, 3),
            "host_issue_ms_per_step": round(1e3 * host / args.steps, 3), "steps": args.steps, "warmup": args.warmup, "final_loss": round(final_loss, 5),
@@ -472,7 +492,7 @@ def eager_block(model, x, t, args, operands, fused_value=None):
 
 def eager_main(args, ts, model, x, t):
     """`--mode eager`: the line's value IS the reference's loop body through the drop-in modules (no HipTrainStep anywhere)."""
-    blk = eager_block(model, x, t, args, args.operands)
+    blk = eager_block(model, x, t, args, args.operands, dump_dir=args.dump_outputs)
     out = {"metric": METRIC, "value": blk["value"], "unit": "samples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": blk["ms_per_step"], "host_issue_ms_per_step": blk["host_issue_ms_per_step"], "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "mode": "eager",
@@ -483,7 +503,7 @@ def eager_main(args, ts, model, x, t):
            "arith": "fp32 via 3 x bf16 split, 6 MFMA terms, fp32 accumulate" if args.operands == "split" else "fp32 MFMA"}
     if (args.batch, args.height, args.width) != (16, 450, 800):
         out["metric"] = "training samples/sec, %s b=%d %dx%d rgbd" % (args.arch, args.batch, args.height, args.width)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.arch, args.batch, args.height, args.width)
     print(json.dumps(out), flush=True)
 
@@ -505,6 +525,14 @@ def main():
                     help="headline = resnet18_latefusion (BASELINE configs[1]); the multistage arch is configs[3] (use --batch 8)")
     ap.add_argument("--graph", action="store_true", help="replay the step as hipGraphs (slower than plain stream launches here)")
     ap.add_argument("--no-graph", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result of the timed steps, also measure what the line carries beside it: `roofline` (instrumented eager "
+                         "pass + in-step shader clock / socket power), `alt_fp32_mfma`, `alt_eager` and `cpu_baseline`.  Off by default: a "
+                         "plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the --no-* switches "
+                         "below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned -- loss, prediction, updated parameters (a fixed seeded "
+                         "sample of the larger ones) -- as DIR/<name>.npy in float32; identical inputs from run to run")
     ap.add_argument("--no-alt", action="store_true", help="skip the extra `alt_fp32_mfma` measurement (the same workload on the plain fp32-MFMA plan; also skipped by "
                                                         "--no-roofline / --no-cpu-baseline, i.e. by the profiling command lines)")
     ap.add_argument("--operands", default=None, choices=["fp32", "bf16", "split"],
@@ -537,6 +565,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the multi-rank plumbing (self-launch, rendezvous, bucketed exchange, JSON line) over gloo")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config if args.config is not None else 2]
     args.arch = args.arch or cfg[0]
     args.batch = args.batch or (cfg[1] if args.config is not None or args.arch == cfg[0] else 8)
@@ -620,7 +650,7 @@ def main():
     marks[0].record()
     for k in range(args.steps):
         h0 = time.perf_counter()
-        loss, _ = ts.step(x, t)
+        loss, pred = ts.step(x, t)
         host_issue += time.perf_counter() - h0
         marks[k + 1].record()
     sync()
@@ -633,6 +663,8 @@ def main():
         per_rank_ms = [1e3 * b.item() / args.steps for b in box]
         dt = max(b.item() for b in box)
     final_loss = float(loss.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, pred, model.parameters())
     # self-verification of the data-parallel run (outside the timed region; one 16-byte all-gather): every rank must hold the SAME
     # parameters after the timed steps (checksum = integer sum of the arena's bit patterns, exact), the per-rank losses differ only
     # through the rank-distinct data, and RCCL's own communicator reports the world size the line claims
@@ -694,7 +726,7 @@ def main():
     out["arith"] = ("fp32 via 3 x bf16 split, 6 MFMA terms, fp32 accumulate" if split else "bf16 storage + bf16 MFMA" if args.storage == "bf16"
                     else "bf16 MFMA operands, fp32 tensors" if bf16 else "fp32 MFMA")
     per_gpu = out["value"] / world
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         agg, fam = instrumented_pass(ts)
         name, (ms, n, flops, nbytes) = max(agg.items(), key=lambda kv: kv[1][0])
         suffix = {("fp32", "fp32"): "_fp32_mfma", ("bf16", "bf16"): "_bf16_storage", ("split", "fp32"): ""}.get((args.operands, args.storage))
@@ -784,7 +816,7 @@ def main():
                     out["roofline"]["frac_of_sustained"] = round(out["roofline"]["achieved"] / sus, 4)
             except Exception as e:                          # noqa: BLE001 -- diagnostics never take the metric down
                 out["roofline"]["shader_clock_mhz"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if (rank == 0 and world == 1 and args.operands == "split" and args.storage == "fp32" and not args.no_alt and not args.graph
+    if (rank == 0 and world == 1 and args.full and args.operands == "split" and args.storage == "fp32" and not args.no_alt and not args.graph
             and not args.no_roofline and not args.no_cpu_baseline and os.environ.get("RD_FORCE_DP") != "1"):
         # the same workload once more on the plain fp32-MFMA plan (every convolution on v_mfma_f32_32x32x2_f32), timed the same way in
         # this process, reported NEXT TO the metric -- `value` above is the default (split) plan and is not affected
@@ -819,7 +851,7 @@ def main():
             ts2.close()
         except Exception as e:      # the alternative line must never take the metric down with it
             out["alt_fp32_mfma"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if (rank == 0 and world == 1 and args.arch == "resnet18_latefusion" and args.storage == "fp32" and args.operands in ("split", "fp32")
+    if (rank == 0 and world == 1 and args.full and args.arch == "resnet18_latefusion" and args.storage == "fp32" and args.operands in ("split", "fp32")
             and not args.no_alt and not args.graph and not args.no_roofline and os.environ.get("RD_FORCE_DP") != "1"):
         # the drop-in route of INTEGRATION.md section 1, measured: the reference's loop body verbatim on the same model
         try:
@@ -837,7 +869,7 @@ def main():
         rd_comm.destroy()
     C.CDLL(None).fflush(None)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.arch, args.batch, args.height, args.width)
         print(json.dumps(out), flush=True)
     if torch.distributed.is_available() and torch.distributed.is_initialized():

@@ -100,11 +100,11 @@ def _install_shims():
 
 
 def _np(t):
-    return t.detach().cpu().numpy().astype(np.float32)
+    return t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
 
 
 def _stats(t):
-    t = t.detach().float()
+    t = t.detach() if t.dtype == torch.float64 else t.detach().float()
     return np.array([t.mean().item(), t.abs().mean().item(), t.abs().max().item()], dtype=np.float64)
 
 
@@ -125,13 +125,21 @@ FULL_BUFFERS = ("bn1.running_mean", "bn1.running_var", "bn1_depth.running_mean",
                 "layer2.0.downsample.1.running_mean")
 
 
-def latefusion_case(ResNet_latefusion, MaskedL1Loss, batch, h, w, seed, sub, dense_small):
+def latefusion_case(ResNet_latefusion, MaskedL1Loss, batch, h, w, seed, sub, dense_small, dtype=torch.float32):
+    """dtype=torch.float64: the same case with the model, batches and optimizer state in double precision (the procedural fp32
+    weights cast up) -- a pin whose fp32 reduction-order noise (host CPU, thread count) is far below its tolerance."""
     out = {}
     torch.manual_seed(0)
     model = ResNet_latefusion(18, "upproj", [h, w], 4, False)
     procedural_fill_(model)
+    model.to(dtype)
+    for m in model.modules():           # constant kernels held as plain tensor attributes (Unpool.weights) follow the dtype too
+        for k, v in list(vars(m).items()):
+            if isinstance(v, torch.Tensor) and v.is_floating_point():
+                setattr(m, k, v.to(dtype))
     ref_px = h * w if dense_small else 450 * 800
     x, t = make_batch(batch, h, w, seed, ref_pixels=ref_px)
+    x, t = x.to(dtype), t.to(dtype)
     crit = MaskedL1Loss()
 
     model.eval()
@@ -167,6 +175,7 @@ def latefusion_case(ResNet_latefusion, MaskedL1Loss, batch, h, w, seed, sub, den
     out["nbt1"] = np.array([int(sd["bn1.num_batches_tracked"])])
     # second step on a fresh batch
     x2, t2 = make_batch(batch, h, w, seed + 1, ref_pixels=ref_px)
+    x2, t2 = x2.to(dtype), t2.to(dtype)
     y2 = model(x2)
     loss2 = crit(y2, t2)
     opt.zero_grad()
@@ -335,6 +344,13 @@ def main():
     for k in [k for k in full if k.startswith(("grad/", "param2/")) and full[k].size > 4096]:
         del full[k]
     np.savez_compressed(os.path.join(HERE, "latefusion_full.npz"), **full)
+    # the same two cases in float64: what tests/test_oracle_golden.py pins the oracle to on any host
+    np.savez_compressed(os.path.join(HERE, "latefusion_small_f64.npz"),
+                        **latefusion_case(models.ResNet_latefusion, crit_mod.MaskedL1Loss, 2, 97, 161, 4321, 1, True, torch.float64))
+    full = latefusion_case(models.ResNet_latefusion, crit_mod.MaskedL1Loss, 2, 450, 800, 1234, 8, False, torch.float64)
+    for k in [k for k in full if k.startswith(("grad/", "param2/")) and full[k].size > 4096]:
+        del full[k]
+    np.savez_compressed(os.path.join(HERE, "latefusion_full_f64.npz"), **full)
     multi = multistage_case(mm.ResNet_multistage, crit_mod.MaskedL1Loss, crit_mod.SmoothnessLoss, 2, 97, 161, 777, 1)
     np.savez_compressed(os.path.join(HERE, "multistage_small.npz"), **multi)
     # config 4's own geometry (the reference's 450x800 multistage smoke, multistage_model.py:279-287), maps strided by 8

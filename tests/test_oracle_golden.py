@@ -1,6 +1,8 @@
 """Pins the CPU oracle to the real reference: the oracle re-runs the exact case functions that
 tests/golden/make_golden.py ran on the imported reference and must reproduce the committed vectors.
-Same torch ops on both sides -> tolerance 1e-6 relative."""
+Same torch ops on both sides -> tolerance 1e-6 relative.  The two late-fusion cases run in float64 on both sides
+(latefusion_*_f64.npz): in fp32 the net's training step differs by up to ~3e-4 relative between hosts and thread counts (the
+convolution backward's reduction order, amplified by the net -- tests/test_conditioning.py), in float64 by ~1e-14."""
 import importlib.util
 import os
 
@@ -33,24 +35,24 @@ def check_all(got, want, tol, skip=()):
 
 
 def test_latefusion_small(golden_dir):
-    want = np.load(os.path.join(golden_dir, "latefusion_small.npz"))
-    got = mg.latefusion_case(models.ResNet_latefusion, criteria.MaskedL1Loss, 2, 97, 161, 4321, 1, True)
+    want = np.load(os.path.join(golden_dir, "latefusion_small_f64.npz"))
+    got = mg.latefusion_case(models.ResNet_latefusion, criteria.MaskedL1Loss, 2, 97, 161, 4321, 1, True, torch.float64)
     assert list(got["param_names"]) == list(want["param_names"])
     assert list(got["stat_names"]) == [s for s in want["stat_names"] if "unpool" not in s] or \
         set(got["stat_names"]) >= set(s for s in want["stat_names"])
     gs = dict(zip(got["stat_names"], got["stat_values"]))
     for name, val in zip(want["stat_names"], want["stat_values"]):
-        assert rel(gs[name], val) <= 1e-5, name
-    check_all(got, want, 2e-6, skip=("stat_values",))
+        assert rel(gs[name], val) <= 1e-10, name
+    check_all(got, want, 1e-10, skip=("stat_values",))
 
 
 def test_latefusion_full(golden_dir):
-    want = np.load(os.path.join(golden_dir, "latefusion_full.npz"))
-    got = mg.latefusion_case(models.ResNet_latefusion, criteria.MaskedL1Loss, 2, 450, 800, 1234, 8, False)
+    want = np.load(os.path.join(golden_dir, "latefusion_full_f64.npz"))
+    got = mg.latefusion_case(models.ResNet_latefusion, criteria.MaskedL1Loss, 2, 450, 800, 1234, 8, False, torch.float64)
     gs = dict(zip(got["stat_names"], got["stat_values"]))
     for name, val in zip(want["stat_names"], want["stat_values"]):
-        assert rel(gs[name], val) <= 1e-5, name
-    check_all(got, want, 5e-6, skip=("stat_values",))
+        assert rel(gs[name], val) <= 1e-10, name
+    check_all(got, want, 1e-10, skip=("stat_values",))
 
 
 def test_multistage_small(golden_dir):

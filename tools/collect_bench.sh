@@ -1,11 +1,11 @@
 # every bench line kept under profiles/ (run on the GPU box: bash tools/collect_bench.sh; results in gpurun_out/bench/)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/bench; mkdir -p $O; cd $R
-python bench.py 2>/dev/null | tail -1 > $O/bench_c2.json
-python bench.py --config 3 2>/dev/null | tail -1 > $O/bench_c3.json
-python bench.py --config 4 2>/dev/null | tail -1 > $O/bench_c4.json
-python bench.py --config 5 2>/dev/null | tail -1 > $O/bench_c5.json
-python bench.py --operands bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_bf16_operands.json
-python bench.py --config 4 --height 900 --width 1600 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_ms_fp32_900.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_c2.json
+python bench.py --full --config 3 2>/dev/null | tail -1 > $O/bench_c3.json
+python bench.py --full --config 4 2>/dev/null | tail -1 > $O/bench_c4.json
+python bench.py --full --config 5 2>/dev/null | tail -1 > $O/bench_c5.json
+python bench.py --full --operands bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_bf16_operands.json
+python bench.py --full --config 4 --height 900 --width 1600 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_ms_fp32_900.json
 # the launcher path + the data-parallel code path (state broadcast, bucket events, rd_allreduce_bucket, 1/world SGD) on ONE rank
 RD_FORCE_DP=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline --no-roofline 2>/dev/null | grep '^{' | tail -1 > $O/bench_c2_dp1_torchrun.json
 python tools/bench_ops.py > $O/bench_ops_per_layer.txt 2>/dev/null

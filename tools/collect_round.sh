@@ -11,13 +11,13 @@ RD_SLOW=1 timeout 1800 python -m pytest tests -m gpu -q -s --durations=30 > $O/p
 # the margins the parity tests print: worst / median errors per plan, fp64-anchored gradients, the decision-floor table over seeds, the three-step trajectory
 { echo "# collected at git $RD_HEAD: margins printed by RD_SLOW=1 pytest -m gpu -s (tests/test_gpu_margins.py, tests/test_gpu_configs.py, tests/test_gpu_wino.py)"; grep -aE "fp64-anchored|three steps|gradient norms|config4 grad|plain multistage|seed [0-9]+:|clean seeds|wino [0-9]" $O/pytest.txt | sed 's/^[.sF]*//'; } > $O/parity_margins.txt
 # ---- bench lines (JSON, one per file)
-python bench.py 2>/dev/null | tail -1 > $O/bench_c2.json
-python bench.py --operands fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c2_fp32_mfma.json
+python bench.py --full 2>/dev/null | tail -1 > $O/bench_c2.json
+python bench.py --full --operands fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c2_fp32_mfma.json
 python bench.py --mode eager --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_c2_eager.json
-RD_WINO=0 python bench.py --no-cpu-baseline --no-alt --no-clock 2>/dev/null | tail -1 > $O/bench_c2_no_winograd.json
-python bench.py --config 3 2>/dev/null | tail -1 > $O/bench_c3.json
-python bench.py --config 4 2>/dev/null | tail -1 > $O/bench_c4.json
-python bench.py --config 5 2>/dev/null | tail -1 > $O/bench_c5.json
+RD_WINO=0 python bench.py --full --no-cpu-baseline --no-alt --no-clock 2>/dev/null | tail -1 > $O/bench_c2_no_winograd.json
+python bench.py --full --config 3 2>/dev/null | tail -1 > $O/bench_c3.json
+python bench.py --full --config 4 2>/dev/null | tail -1 > $O/bench_c4.json
+python bench.py --full --config 5 2>/dev/null | tail -1 > $O/bench_c5.json
 RD_FORCE_DP=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline --no-roofline 2>/dev/null | grep '^{' | tail -1 > $O/bench_c2_dp1_torchrun.json
 # Winograd A/B in one job on one box (boxes of the pool differ by several percent: only same-job pairs compare)
 { echo "# collected at git $RD_HEAD: Winograd layers on (default planner rule) / off (RD_WINO=0) / everywhere supported (RD_WINO=all), same job, same box"
