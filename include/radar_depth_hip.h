@@ -151,6 +151,19 @@ int rd_gconv_split(const RdConvDesc* d, const float* in, const void* w_split, in
 int rd_gconv_split_stat_tiles(const RdConvDesc* d);
 /* diagnostics: out[0..7] = MT, NT, TH, TW, patch pixels, lds_bytes, workgroups, tap groups of the largest phase */
 int rd_gconv_split_plan_info(const RdConvDesc* d, int32_t* out);
+/* Few-tap phases as a channel-grouped GEMM (csrc/gemm_taps_split.hip): rd_gconv_split's operands, arithmetic and epilogue for
+ * descriptors whose every phase has 1..4 taps, the reduction grouped by (tap, 32 input channels) instead of padded to tap groups of
+ * three.  Cin a multiple of 32, Cout a multiple of 32, both >= 32.  Stat tiles [rd_gemm_taps_split_stat_tiles(d)][2][Cout].
+ * rd_gconv_split never routes here; the plan calls it where rd_gemm_taps_split_preferred says so.
+ * plan_info out[0..7] = MT, NT, rows per tile, 1, 0, lds_bytes, workgroups, taps of the largest phase. */
+int rd_gemm_taps_split_supported(const RdConvDesc* d);
+/* 1 where the kernel gate measured it ahead of the plan's split kernels (one 4-tap phase at input stride 2: a k = 2 transposed
+ * convolution's input gradient), else 0 */
+int rd_gemm_taps_split_preferred(const RdConvDesc* d);
+int rd_gemm_taps_split_stat_tiles(const RdConvDesc* d);
+int rd_gemm_taps_split_plan_info(const RdConvDesc* d, int32_t* out);
+int rd_gemm_taps_split(const RdConvDesc* d, const float* in, const void* w_split, int64_t piece_elems, float* out, const float* bias,
+                       int32_t act, int32_t act_cols, const float* addend, int32_t ld_add, float* stat_partial, void* stream);
 /* Pre-split activations: an fp32 NHWC tensor x[M][C] (row stride ldx) as three bf16 piece planes, each [C/16][M][16], piece_elems
  * elements apart (x = p0 + p1 + p2 exactly).  rd_split_pieces is the stand-alone producer; in the training plan the BatchNorm /
  * activation kernels write the planes from their epilogues (rd_bn_act_p, rd_bn_bwd_apply*_p, rd_bnact_maxpool_fwd_p), so the split
@@ -279,8 +292,9 @@ int rd_pack_weights_bf16(const float* w_oihw, void* packed_bf16, int32_t O, int3
 
 /* All weight tensors of a network in ONE launch.  jobs_dev: device array of
  *   struct { const float* src; float* dst; const float* scale; int32_t O, I, T(=KH*KW), ldc, off, rows_total,
- *            transpose, first_block, quad, pad; }
- *   scale (nullable): per-output-channel factor = folded BatchNorm scale (eval mode); quad 1: row-interleaved gconv
+ *            transpose, first_block, quad, scale_col; }
+ *   scale (nullable): per-output-channel factor = folded BatchNorm scale (eval mode), indexed by the source's dim 0 (O), or by its
+ *   dim 1 (I) when scale_col != 0 (the [Cin, Cout, k, k] weight of a transposed convolution); quad 1: row-interleaved gconv
  *   operand layout, 2: bf16 operand of rd_gconv_bf16, 0: plain [slab][row][col] (the 7x7 stem kernels)
  * (same meaning as rd_pack_weights' arguments); block_job_dev[b] = job index of block b, where job j owns blocks
  * [first_block, first_block + ceil(O*I*T / rd_pack_chunk())).  Both arrays are built once by the host plan. */

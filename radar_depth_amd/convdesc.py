@@ -11,6 +11,12 @@ Every convolution on the hot path and every input-gradient of one is a list of a
   upproj_fwd    Unpool(2) + 5x5 conv as 4 phases with 9/6/6/4 taps on the LOW-RES input
                 (models.py:13-27,181-209; the zero-skipping identity of SURVEY.md 8a row 6)
   upproj_dgrad  its input gradient: one 25-tap phase reading dout with input stride 2
+  deconv_fwd    nn.ConvTranspose2d(k, stride 2, pad (k-1)//2, output_padding k%2) (models.py:115-146), the adjoint of
+                Conv2d(k, stride 2, pad (k-1)//2): its weight [Cin,Cout,k,k] read as that conv's OIHW weight, the forward is
+                the conv's input gradient (4 parity phases over the low-res input, out_stride 2) ...
+  deconv_dgrad  ... its input gradient is the conv's forward (one k*k-tap phase, in_stride 2) ...
+  deconv_wgrad  ... and its weight gradient the conv's weight gradient with dy as the input and x as the output gradient, which
+                lands directly in the [Cin][Cout][kh][kw] layout
 """
 from ._lib import RD_MAX_PHASES, RD_MAX_TAPS, RdConvDesc, RdPhase
 
@@ -93,6 +99,30 @@ def upproj_dgrad(N, H, W, Cin, Cout, ld_dy=None, ld_dx=None):
     """dx[i,j] = sum_{kh,kw} dout[2i+2-kh, 2j+2-kw] @ W[kh,kw]^T : 'input' dout [N,2H,2W,Cout], 'output' dx [N,H,W,Cin]."""
     taps = [(2 - kh, 2 - kw, kh * 5 + kw) for kh in range(5) for kw in range(5)]
     return _desc(N, 2 * H, 2 * W, Cout, ld_dy or Cout, H, W, Cin, ld_dx or Cin, 2, 1, [_phase(taps, H, W)])
+
+
+def deconv_pad(k):
+    return (k - 1) // 2
+
+
+def deconv_fwd(N, H, W, Cin, Cout, k, ldi=None, ldo=None):
+    """x [N,H,W,Cin] -> out [N,2H,2W,Cout]; weights packed transposed ([slab][Cin][Cout]: the adjoint conv's dgrad operand)."""
+    d, zero_fill = conv_dgrad(N, 2 * H, 2 * W, Cout, Cin, k, 2, deconv_pad(k), ld_dy=ldi or Cin, ld_dx=ldo or Cout)
+    assert not zero_fill and (d.Hi, d.Wi) == (H, W)
+    return d
+
+
+def deconv_dgrad(N, H, W, Cin, Cout, k, ld_dy=None, ld_dx=None):
+    """dy [N,2H,2W,Cout] -> dx [N,H,W,Cin]; weights packed plain ([slab][Cout][Cin]: the adjoint conv's forward operand)."""
+    d = conv_fwd(N, 2 * H, 2 * W, Cout, Cin, k, 2, deconv_pad(k), ldi=ld_dy or Cout, ldo=ld_dx or Cin)
+    assert (d.Ho, d.Wo) == (H, W)
+    return d
+
+
+def deconv_wgrad(N, H, W, Cin, Cout, k, ld_dy=None, ld_x=None):
+    """Weight-gradient descriptor: the adjoint conv's forward with 'input' dy [N,2H,2W,Cout] and 'output gradient' x [N,H,W,Cin]; its
+    slabs [k*k][Cout][Cin] reduce to the OIHW gradient of an [O=Cin, I=Cout, k, k] weight -- the ConvTranspose2d weight itself."""
+    return deconv_dgrad(N, H, W, Cin, Cout, k, ld_dy=ld_dy, ld_dx=ld_x)
 
 
 def desc_to_dict(d):

@@ -56,8 +56,10 @@ struct PackJob {
     float* dst;
     const float* scale;   // optional per-output-channel factor (eval mode: folded BatchNorm scale), may be null
     int O, I, T, ldc, off, rows_total, transpose, first_block;
-    int quad, pad_;       // 1: gconv operand layout (rows interleaved by four); 2: bf16 operand (by eight); 0: plain [slab][row][col] (stem kernels)
+    int quad;             // 1: gconv operand layout (rows interleaved by four); 2: bf16 operand (by eight); 0: plain [slab][row][col] (stem kernels)
                           // 3: three bf16 piece planes of the bf16 layout (gconv_split.hip), plane stride T * rows * ldc elements
+    int scale_col;        // 1: scale[] is indexed by the source's dim 1 (i), not dim 0 (o): the output channels of a transposed
+                          // convolution's [Cin, Cout, k, k] weight (eval-mode BatchNorm fold of a DeConv layer)
 };
 // the three bf16 pieces of an fp32 value (gconv_split.hip): v = p0 + p1 + p2 exactly
 __device__ __forceinline__ void store_split3(__bf16* dst, int64_t idx, int64_t plane, float v) {
@@ -91,7 +93,7 @@ __device__ __forceinline__ void pack_units_bf16(const PackJob& j, int64_t u) {
         for (int r = 0; r < 8; ++r) {
             const int o = j.transpose ? r8 * 8 + r : col, i = j.transpose ? col : r8 * 8 + r;
             v[r] = j.src[((int64_t)o * j.I + i) * j.T + t];
-            if (j.scale) v[r] *= j.scale[o];
+            if (j.scale) v[r] *= j.scale[j.scale_col ? i : o];
         }
         const int64_t idx = packed_index_bf16(t, rows_total, row0, j.ldc, colp);      // (row0 % 8 == 0: the unit's first element)
         unsigned w0[4], w1[4], w2[4];
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const PackJob
             const int o = (int)(e - r * (unsigned)j.O);
             const int t = (int)(r / (unsigned)j.I), i = (int)(r - (r / (unsigned)j.I) * (unsigned)j.I);
             float v = j.src[((int64_t)o * j.I + i) * j.T + t];
-            if (j.scale) v *= j.scale[o];
+            if (j.scale) v *= j.scale[j.scale_col ? i : o];
             if (j.quad == 3) store_split3(reinterpret_cast<__bf16*>(j.dst), packed_index_bf16(t, j.I, i, j.ldc, j.off + o), (int64_t)j.T * j.I * j.ldc, v);
             else if (j.quad == 2) reinterpret_cast<__bf16*>(j.dst)[packed_index_bf16(t, j.I, i, j.ldc, j.off + o)] = (__bf16)v;
             else j.dst[packed_index(j.quad, t, j.I, i, j.ldc, j.off + o)] = v;
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const PackJob
             const int i = (int)(e - r * (unsigned)j.I);
             const int t = (int)(r / (unsigned)j.O), o = (int)(r - (r / (unsigned)j.O) * (unsigned)j.O);
             float v = j.src[((int64_t)o * j.I + i) * j.T + t];
-            if (j.scale) v *= j.scale[o];
+            if (j.scale) v *= j.scale[j.scale_col ? i : o];
             if (j.quad == 3) store_split3(reinterpret_cast<__bf16*>(j.dst), packed_index_bf16(t, j.rows_total, j.off + o, j.ldc, i), (int64_t)j.T * j.rows_total * j.ldc, v);
             else if (j.quad == 2) reinterpret_cast<__bf16*>(j.dst)[packed_index_bf16(t, j.rows_total, j.off + o, j.ldc, i)] = (__bf16)v;
             else j.dst[packed_index(j.quad, t, j.rows_total, j.off + o, j.ldc, i)] = v;

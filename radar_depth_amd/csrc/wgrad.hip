@@ -616,7 +616,9 @@ static int plan_wgrad(const RdConvDesc& d_in, WgradPlan& pl, WgradArgs* out, int
     S = S_all;
     // rectangular stencil in row-major tap order -> the immediate-offset kernel, whose patch pitch is fixed at WG_PITCH
     const int rw = dw_max - dw_min + 1;
-    bool k3 = d.n_phases == 1 && ntaps == rw * (dh_max - dh_min + 1) && (ntaps == 9 || (ph >= 0 && (ntaps == 6 || ntaps == 4)));
+    // (a single-phase 2x2 stencil: the weight gradient of a k = 2 transposed convolution, read as its adjoint stride-2 convolution)
+    bool k3 = d.n_phases == 1 && ntaps == rw * (dh_max - dh_min + 1) &&
+              (ntaps == 9 || (ph >= 0 && (ntaps == 6 || ntaps == 4)) || (ntaps == 4 && rw == 2 && d.out_stride == 1));
     for (int t = 0; k3 && t < ntaps; ++t) k3 = P0.dh[t] - dh_min == t / rw && P0.dw[t] - dw_min == t % rw;
     static const char* nok3 = getenv("RD_WGRAD_NOK3");
     if (nok3) k3 = false;

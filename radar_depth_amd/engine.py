@@ -86,6 +86,25 @@ def _p(t):
 SPLIT_BNB_DEFAULT = "0"
 
 
+class _ColScale:
+    """Folded BatchNorm scale of a transposed convolution: its output channels run along dim 1 of the [Cin, Cout, k, k] weight, so the
+    pack job indexes the scale by column (PackJob.scale_col in csrc/layout.hip)."""
+    __slots__ = ("t",)
+
+    def __init__(self, t):
+        self.t = t
+
+    def data_ptr(self):
+        return self.t.data_ptr()
+
+
+# descriptor kinds of conv_fwd / conv_bwd / conv_bn_eval: weights [(w, column offset)], w OIHW except for "deconv" ([Cin, Cout, k, k])
+#   conv    nn.Conv2d k x k, stride, pad (convdesc.conv_fwd / conv_dgrad)
+#   upproj  Unpool(2) + 5x5 conv folded into four phases (convdesc.upproj_fwd / upproj_dgrad): UpProj and UpConv layers
+#   deconv  nn.ConvTranspose2d(k, stride 2, pad (k-1)//2, output_padding k%2) as its adjoint conv (convdesc.deconv_*): DeConv layers
+CONV_KINDS = ("conv", "upproj", "deconv")
+
+
 class LateFusionPlan:
     def __init__(self, module, batch, height, width, train=True, depth_planes=None, x_source=None, dense_grad_dst=None,
                  dry_run=False, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False):
@@ -330,13 +349,18 @@ class LateFusionPlan:
             check(int(n), "rd_gconv_workspace_floats(%s)" % name)
         return self.buf(int(n)) if n > 0 else None
 
-    def conv_fwd(self, name, x, weights, k, stride, pad, out=None, upproj=False, lst=None):
-        """weights: list of (param OIHW, column offset).  Returns (raw Act, ctx)."""
+    def conv_fwd(self, name, x, weights, k, stride, pad, out=None, kind="conv", lst=None):
+        """weights: list of (param, column offset), OIHW params except for kind "deconv" (CONV_KINDS).  Returns (raw Act, ctx)."""
+        assert kind in CONV_KINDS
         lst = self.fwd if lst is None else lst
         N, H, W = x.N, x.H, x.W
-        cout = sum(w.shape[0] for w, _ in weights)
+        deconv = kind == "deconv"
+        cout = sum(w.shape[1 if deconv else 0] for w, _ in weights)
         cin = x.C
-        if upproj:
+        if deconv:
+            assert len(weights) == 1 and weights[0][1] == 0 and stride == 2 and pad == cd.deconv_pad(k)
+            d = cd.deconv_fwd(N, H, W, cin, cout, k, ldi=x.ld)
+        elif kind == "upproj":
             d = cd.upproj_fwd(N, H, W, cin, cout, ldi=x.ld)
         else:
             d = cd.conv_fwd(N, H, W, cin, cout, k, stride, pad, ldi=x.ld)
@@ -353,12 +377,13 @@ class LateFusionPlan:
         # it ahead of the direct split kernels (rd_wino_preferred: 512-channel layers, small maps with <= 128 channels); forward and input
         # gradient decided separately (the input gradient is the same kernel on the flipped operand, channels swapped)
         wino_f = wino_d = False
-        if self.split and self.train and not upproj and k == 3 and stride == 1 and pad == 1 and len(weights) == 1 and weights[0][1] == 0:
+        if self.split and self.train and kind == "conv" and k == 3 and stride == 1 and pad == 1 and len(weights) == 1 and weights[0][1] == 0:
             wino_f = self.L.rd_wino_preferred(H, W, cin, cout, x.ld, out.ld if out is not None else cout) == 1
             wino_d = self.L.rd_wino_preferred(H, W, cout, cin, cout, cin) == 1
         if self.split:
             sp_f = self.L.rd_gconv_split_supported(C.byref(d)) == 1
-            dd0 = (cd.upproj_dgrad(N, H, W, cin, cout) if upproj else cd.conv_dgrad(N, H, W, cin, cout, k, stride, pad)[0])
+            dd0 = (cd.deconv_dgrad(N, H, W, cin, cout, k) if deconv else cd.upproj_dgrad(N, H, W, cin, cout) if kind == "upproj"
+                   else cd.conv_dgrad(N, H, W, cin, cout, k, stride, pad)[0])
             sp_d = self.L.rd_gconv_split_supported(C.byref(dd0)) == 1
             # the pre-split form (operand split by its producer, gconv_sp2_kernel) where the library expects it to win even after the
             # producer's extra piece pass -- incl. 32-channel layers rd_gconv_split does not serve
@@ -373,6 +398,10 @@ class LateFusionPlan:
                 sp_f = pre_f = False
             if wino_d:
                 sp_d = pre_d = False
+        # the few-tap channel-grouped kernel (csrc/gemm_taps_split.hip) where its gate measured it ahead: deconv2's input gradient
+        taps_d = self.split and deconv and self.L.rd_gemm_taps_split_preferred(C.byref(dd0)) == 1
+        if taps_d:
+            sp_d, pre_d = True, False
         self.L.rd_wino_packed_bytes.restype = C.c_int64
         uf = ud = None
         if wino_f:
@@ -389,6 +418,12 @@ class LateFusionPlan:
             wd = self.buf(3, S, cout, cin, dtype=torch.bfloat16) if sp_d else self.buf(S, cout, cin, dtype=wdt)
         for w, off in weights:
             o, i, kh, kw = w.shape
+            if deconv:
+                # the [Cin, Cout, k, k] weight read as the adjoint conv's OIHW weight (O = cin, I = cout): the forward is that conv's input
+                # gradient (transposed operand [slab][cin][cout]), the input gradient its forward (plain operand [slab][cout][cin])
+                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, 0, cin, 1, None, 3 if sp_f else quad))
+                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, 0, i, 0, None, 3 if sp_d else quad))
+                continue
             if not wino_f:
                 self.pack_jobs.append((w, wp, o, i, kh * kw, cout, off, i, 0, None, 3 if sp_f else quad))
             if not wino_d:
@@ -430,8 +465,9 @@ class LateFusionPlan:
             self.op(lst, name, self.L.rd_gconv_ws, C.byref(d), x.ptr, _p(wp), out.ptr, C.c_void_p(0), 0, _p(stat), _p(ws), self.stream)
         self.taps[name] = out
         self.meta[name] = ("wino" if wino_f else "gconv_split_pre" if pre_f else "gconv_split" if sp_f else "gconv_bf16" if self.bf16 else "conv16_split" if c16 else "gconv", d)
-        ctx = dict(name=name, d=d, x=x, out=out, weights=weights, wd=wd, k=k, stride=stride, pad=pad, upproj=upproj,
-                   stat=stat, tiles=tiles, cin=cin, cout=cout, split_dgrad=sp_d, pre_dgrad=self.split and pre_d, wino_dgrad=wino_d, ud=ud)
+        ctx = dict(name=name, d=d, x=x, out=out, weights=weights, wd=wd, k=k, stride=stride, pad=pad, kind=kind,
+                   stat=stat, tiles=tiles, cin=cin, cout=cout, split_dgrad=sp_d, pre_dgrad=self.split and pre_d, wino_dgrad=wino_d, ud=ud,
+                   taps_dgrad=self.split and taps_d)
         return out, ctx
 
     def _c16_split(self, d):
@@ -446,10 +482,18 @@ class LateFusionPlan:
         self.bnb_out = None
         name, d, x = ctx["name"], ctx["d"], ctx["x"]
         N, H, W, cin, cout, k = x.N, x.H, x.W, ctx["cin"], ctx["cout"], ctx["k"]
-        # wgrad uses the forward descriptor with dout's stride
-        dwd = type(d)()
-        C.memmove(C.byref(dwd), C.byref(d), C.sizeof(d))
-        dwd.ldo = dout.ld
+        deconv = ctx["kind"] == "deconv"
+        if deconv:
+            # a transposed convolution's weight gradient is its adjoint conv's, with dout as that conv's input and x as its output
+            # gradient: the slabs [k*k][cout][cin] reduce straight into the [Cin, Cout, k, k] weight (convdesc.deconv_wgrad)
+            dwd = cd.deconv_wgrad(N, H, W, cin, cout, k, ld_dy=dout.ld, ld_x=x.ld)
+            w_in, w_dout = dout, x
+        else:
+            # wgrad uses the forward descriptor with dout's stride
+            dwd = type(d)()
+            C.memmove(C.byref(dwd), C.byref(d), C.sizeof(d))
+            dwd.ldo = dout.ld
+            w_in, w_dout = x, dout
         self.keep.append(dwd)
         # bf16 plans: the weight gradients run on the bf16 matrix cores as well (3x3 / 1x1 at both strides, UpProj 5x5); what the
         # bf16 kernel cannot decompose keeps the fp32 kernel
@@ -478,7 +522,7 @@ class LateFusionPlan:
         # stand-alone split pass (an operand without a piece-writing producer) is ordered before both consumers
         # (the weight gradient keeps splitting while it stages: its pre-split form measured 0.8-0.9x, profiles/r04_bench_wgrad_split.txt;
         #  RD_WGRAD_PRE=1 opts in)
-        wg_pre = (wg_split and os.environ.get("RD_WGRAD_PRE", "0") == "1" and self._pre_ok(x) and self._pre_ok(dout)
+        wg_pre = (wg_split and not deconv and os.environ.get("RD_WGRAD_PRE", "0") == "1" and self._pre_ok(x) and self._pre_ok(dout)
                   and self.L.rd_wgrad_split_pre_supported(C.byref(dwd)) == 1)
         sp_d0 = bool(ctx.get("split_dgrad"))
         dg_pre = need_dx and sp_d0 and bool(ctx.get("pre_dgrad")) and self._pre_ok(dout)
@@ -496,11 +540,11 @@ class LateFusionPlan:
             self.edge(self.bwd, name + ".fork_wgrad", cur, wst)
             with self.on(wst):
                 if wg_bf16:
-                    self.op(self.bwd, name + ".wgrad", self.L.rd_wgrad_bf16_t, self.dt, C.byref(dwd), x.ptr, dout.ptr, _p(ws), self.stream)
+                    self.op(self.bwd, name + ".wgrad", self.L.rd_wgrad_bf16_t, self.dt, C.byref(dwd), w_in.ptr, w_dout.ptr, _p(ws), self.stream)
                 elif wg_pre:
                     self.op(self.bwd, name + ".wgrad", self.L.rd_wgrad_split_pre, C.byref(dwd), xp, xplane, yp, yplane, _p(ws), self.stream)
                 else:
-                    self.op(self.bwd, name + ".wgrad", f_wgrad, C.byref(dwd), x.ptr, dout.ptr, _p(ws), self.stream)
+                    self.op(self.bwd, name + ".wgrad", f_wgrad, C.byref(dwd), w_in.ptr, w_dout.ptr, _p(ws), self.stream)
                 self.meta[name + ".wgrad"] = ("wgrad_split_pre" if wg_pre else fam, dwd)
                 for w, off in sorted(ctx["weights"], key=lambda t: t[1]):
                     o, i, kh, kw = w.shape
@@ -526,7 +570,9 @@ class LateFusionPlan:
         dx_owned = dx is None
         if dx is None:
             dx = self.act(N, H, W, cin)
-        if ctx["upproj"]:
+        if deconv:
+            dd, zero_fill = cd.deconv_dgrad(N, H, W, cin, cout, k, ld_dy=dout.ld, ld_dx=dx.ld), False
+        elif ctx["kind"] == "upproj":
             dd, zero_fill = cd.upproj_dgrad(N, H, W, cin, cout, ld_dy=dout.ld, ld_dx=dx.ld), False
         else:
             dd, zero_fill = cd.conv_dgrad(N, H, W, cin, cout, k, ctx["stride"], ctx["pad"], ld_dy=dout.ld, ld_dx=dx.ld)
@@ -572,6 +618,16 @@ class LateFusionPlan:
             else:
                 self.op(self.bwd, name + ".dgrad", self.L.rd_wino_conv3x3, dout.ptr, N, H, W, cout, dout.ld, _p(ctx["ud"]), dx.ptr, cin, dx.ld,
                         addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0, C.c_void_p(0), self.stream)
+            if late:
+                launch_wgrad()
+            return dx
+        if ctx.get("taps_dgrad"):
+            if self.L.rd_gemm_taps_split_supported(C.byref(dd)) != 1:
+                raise RuntimeError("%s: planned on rd_gemm_taps_split, but the library does not serve the final input-gradient descriptor" % name)
+            self.meta[name + ".dgrad"] = ("gemm_taps_split", dd)
+            self.op(self.bwd, name + ".dgrad", self.L.rd_gemm_taps_split, C.byref(dd), dout.ptr, _p(ctx["wd"]), C.c_int64(k * k * cin * cout), dx.ptr,
+                    C.c_void_p(0), 0, 0, addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
+                    C.c_void_p(0), self.stream)
             if late:
                 launch_wgrad()
             return dx
@@ -664,12 +720,20 @@ class LateFusionPlan:
             self.reduce_batches.append((len(self.bwd_segments) if hasattr(self, "bwd_segments") else 0, k, [j[0] for j in jobs]))
 
     # ------------------------------------------------------------------ inference: conv + folded BatchNorm (+ReLU, +residual)
-    def conv_bn_eval(self, name, x, parts, k, stride, pad, act, act_cols=None, addend=None, out=None, upproj=False):
+    def conv_bn_eval(self, name, x, parts, k, stride, pad, act, act_cols=None, addend=None, out=None, kind="conv"):
         """Eval-mode conv+BN(+act)(+residual) as ONE kernel: the BatchNorm scale gamma/sqrt(var+eps)
-        is folded into the packed weights, its shift is the epilogue bias.  parts: [(conv weight, column offset, bn)]."""
+        is folded into the packed weights, its shift is the epilogue bias.  parts: [(conv weight, column offset, bn)]; kind: CONV_KINDS."""
+        assert kind in CONV_KINDS
         N, H, W, cin = x.N, x.H, x.W, x.C
-        cout = sum(w.shape[0] for w, _, _ in parts)
-        d = cd.upproj_fwd(N, H, W, cin, cout, ldi=x.ld) if upproj else cd.conv_fwd(N, H, W, cin, cout, k, stride, pad, ldi=x.ld)
+        deconv = kind == "deconv"
+        cout = sum(w.shape[1 if deconv else 0] for w, _, _ in parts)
+        if deconv:
+            assert len(parts) == 1 and parts[0][1] == 0 and stride == 2 and pad == cd.deconv_pad(k)
+            d = cd.deconv_fwd(N, H, W, cin, cout, k, ldi=x.ld)
+        elif kind == "upproj":
+            d = cd.upproj_fwd(N, H, W, cin, cout, ldi=x.ld)
+        else:
+            d = cd.conv_fwd(N, H, W, cin, cout, k, stride, pad, ldi=x.ld)
         if out is None:
             out = self.act(N, d.Ho, d.Wo, cout)
         d.ldo = out.ld
@@ -680,6 +744,11 @@ class LateFusionPlan:
             o, i, kh, kw = w.shape
             sc = C.c_void_p(scale.data_ptr() + 4 * off)
             sh = C.c_void_p(bias.data_ptr() + 4 * off)
+            if deconv:
+                # output channels = dim 1 of the [Cin, Cout, k, k] weight: the fold scales columns of the transposed operand
+                self.evalcoef_jobs.append((i, bn, sc, sh))
+                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, 0, cin, 1, _ColScale(scale[:i]), 2 if self.bf16 else 1))
+                continue
             self.evalcoef_jobs.append((o, bn, sc, sh))       # all folded BatchNorms: ONE launch (see _finish_pack_jobs)
             self.pack_jobs.append((w, wp, o, i, kh * kw, cout, off, i, 0, scale[off:off + o], 2 if self.bf16 else 1))
         self.keep += [d, scale]
@@ -969,12 +1038,12 @@ class LateFusionPlan:
         ub, bb = mod.upper_branch, mod.bottom_branch
         if not self.train:
             R = self.conv_bn_eval(name + ".conv5x5", x, [(ub.conv1.weight, 0, ub.batchnorm1), (bb.conv.weight, half, bb.batchnorm)], 5, 1, 2,
-                                  ACT_RELU, act_cols=half, upproj=True)
+                                  ACT_RELU, act_cols=half, kind="upproj")
             y = self.conv_bn_eval(name + ".upper_branch.conv2", R.chan(0, half), [(ub.conv2.weight, 0, ub.batchnorm2)], 3, 1, 1, ACT_RELU,
                                   addend=R.chan(half, half))
             self.taps[name] = y
             return y, None
-        R, cR = self.conv_fwd(name + ".conv5x5", x, [(ub.conv1.weight, 0), (bb.conv.weight, half)], 5, 1, 2, upproj=True)
+        R, cR = self.conv_fwd(name + ".conv5x5", x, [(ub.conv1.weight, 0), (bb.conv.weight, half)], 5, 1, 2, kind="upproj")
         M = R.M
         co_u1 = self.bn_coeffs(name + ".upper_branch.batchnorm1", ub.batchnorm1, cR["stat"], cR["tiles"], Cc, 0, M)
         co_b = self.bn_coeffs(name + ".bottom_branch.batchnorm", bb.batchnorm, cR["stat"], cR["tiles"], Cc, half, M)
@@ -1005,6 +1074,58 @@ class LateFusionPlan:
         self.taps["grad_R:" + name] = dR
         self.taps["grad_y1:" + name] = dy1
         return dx
+
+    def _deconv(self, name, mod, x):
+        """DeConv layer (models.py:122-133): ConvTranspose2d(k, stride 2) -> BatchNorm -> ReLU, the BatchNorm statistics from the
+        transposed convolution's epilogue."""
+        conv, bn = mod[0], mod.batchnorm
+        k = conv.kernel_size[0]
+        cname = "%s.deconv%d" % (name, k)
+        if not self.train:
+            y = self.conv_bn_eval(cname, x, [(conv.weight, 0, bn)], k, 2, cd.deconv_pad(k), ACT_RELU, kind="deconv")
+            self.taps[name] = y
+            return y, None
+        r, c = self.conv_fwd(cname, x, [(conv.weight, 0)], k, 2, cd.deconv_pad(k), kind="deconv")
+        co = self.bn_coeffs(name + ".batchnorm", bn, c["stat"], c["tiles"], r.C, 0, r.M)
+        y = self.bn_act(name, r, co, ACT_RELU)
+        return y, dict(name=name, r=r, c=c, co=co, y=y)
+
+    def _upconv(self, name, mod, x):
+        """UpConv layer (models.py:150-158): Unpool -> 5x5 conv -> BatchNorm -> ReLU, the unpool folded into the four-phase
+        convolution of the UpProj modules (Cout = Cin/2)."""
+        conv, bn = mod.conv, mod.batchnorm
+        if not self.train:
+            y = self.conv_bn_eval(name + ".conv", x, [(conv.weight, 0, bn)], 5, 1, 2, ACT_RELU, kind="upproj")
+            self.taps[name] = y
+            return y, None
+        r, c = self.conv_fwd(name + ".conv", x, [(conv.weight, 0)], 5, 1, 2, kind="upproj")
+        co = self.bn_coeffs(name + ".batchnorm", bn, c["stat"], c["tiles"], r.C, 0, r.M)
+        y = self.bn_act(name, r, co, ACT_RELU)
+        return y, dict(name=name, r=r, c=c, co=co, y=y)
+
+    def _conv_bn_relu_bwd(self, ctx, dy):
+        """Backward of a DeConv / UpConv layer: BatchNorm + ReLU backward (sign re-derived from the raw conv output), then the
+        convolution's input and weight gradients."""
+        name = ctx["name"]
+        dr, _ = self.bn_join_bwd(name, dy, ctx["y"], ACT_RELU, ctx["r"], ctx["co"], lone=True)
+        dx = self.conv_bwd(ctx["c"], dr)
+        self.taps["grad_out:" + name] = dy
+        self.taps["grad_in:" + name] = dx
+        return dx
+
+    _deconv_bwd = _upconv_bwd = _conv_bn_relu_bwd
+
+    def _decoder_ops(self, dec):
+        """(layer builder, its backward) of a decoder: UpProj, DeConv (k = 2, 3) or UpConv (models.py:115-230)."""
+        kind = getattr(dec, "_layer_kind", None)
+        if kind not in ("upproj", "deconv", "upconv"):
+            raise NotImplementedError("decoder %s: the MI355X plan serves UpProj, DeConv and UpConv" % type(dec).__name__)
+        if kind != "upproj" and self.bf16:
+            raise NotImplementedError("the bf16-operand and bf16-storage plans serve the upproj decoder only (got %s)" % type(dec).__name__)
+        if kind == "deconv" and dec.layer1[0].kernel_size[0] not in (2, 3):
+            raise NotImplementedError("DeConv kernel size %d: the MI355X plan serves deconv2 and deconv3" % dec.layer1[0].kernel_size[0])
+        return {"upproj": (self._upproj, self._upproj_bwd), "deconv": (self._deconv, self._deconv_bwd),
+                "upconv": (self._upconv, self._upconv_bwd)}[kind]
 
     # ------------------------------------------------------------------ whole network
     def _build(self):
@@ -1077,8 +1198,9 @@ class LateFusionPlan:
             yf = self.conv_bn_eval("conv_fusion", self.cat, [(m.conv_fusion.weight, 0, m.bn_fusion)], 1, 1, 0, ACT_NONE)
             z = self.conv_bn_eval("conv2", yf, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
             self.taps["bn_fusion"], self.taps["bn2"] = yf, z
+            dec_fwd, _ = self._decoder_ops(m.decoder)
             for i, mod in enumerate((m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4), 1):
-                z, _ = self._upproj("decoder.layer%d" % i, mod, z)
+                z, _ = dec_fwd("decoder.layer%d" % i, mod, z)
             self._head(z)
             self._finish_pack_jobs()
             return
@@ -1091,8 +1213,9 @@ class LateFusionPlan:
         self.rf, self.r2 = rf, r2
         # decoder
         self.ups = []
+        dec_fwd, self.dec_bwd = self._decoder_ops(m.decoder)
         for i, mod in enumerate((m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4), 1):
-            z, ctx = self._upproj("decoder.layer%d" % i, mod, z)
+            z, ctx = dec_fwd("decoder.layer%d" % i, mod, z)
             self.ups.append(ctx)
         self._head(z)
         self._finish_pack_jobs()
@@ -1114,7 +1237,7 @@ class LateFusionPlan:
         class Job(C.Structure):
             _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("scale", C.c_void_p), ("O", C.c_int32), ("I", C.c_int32), ("T", C.c_int32),
                         ("ldc", C.c_int32), ("off", C.c_int32), ("rows_total", C.c_int32), ("transpose", C.c_int32),
-                        ("first_block", C.c_int32), ("quad", C.c_int32), ("pad_", C.c_int32)]
+                        ("first_block", C.c_int32), ("quad", C.c_int32), ("scale_col", C.c_int32)]
         if self.evalcoef_jobs:
             class EJob(C.Structure):
                 _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("rm", C.c_void_p), ("rv", C.c_void_p), ("scale", C.c_void_p),
@@ -1137,7 +1260,8 @@ class LateFusionPlan:
             for k, (src, dst, o, i, t, ldc, off, rows, tr, scale, quad) in enumerate(job_list):
                 assert o * i * t < 2 ** 31, "pack_weights_batched indexes one weight tensor with 32-bit arithmetic"
                 n = -(-(o * i * t) // chunk)
-                jobs[k] = Job(src.data_ptr(), dst.data_ptr(), scale.data_ptr() if scale is not None else None, o, i, t, ldc, off, rows, tr, nb, quad, 0)
+                jobs[k] = Job(src.data_ptr(), dst.data_ptr(), scale.data_ptr() if scale is not None else None, o, i, t, ldc, off, rows, tr, nb, quad,
+                              int(isinstance(scale, _ColScale)))
                 block_job += [k] * n
                 nb += n
             raw = np.frombuffer(bytes(jobs), dtype=np.uint8).copy()
@@ -1223,7 +1347,7 @@ class LateFusionPlan:
             self.op(self.bwd, "conv3.wgrad", self.L.rd_head_conv_wgrad_t, self.dt, z.ptr, z.ld, _p(ddm), N, z.H, z.W, z.C,
                     _p(self.grad_of(m.conv3.weight)), _p(ws), self.stream)
         for ctx in reversed(self.ups):
-            dz = self._upproj_bwd(ctx, dz)
+            dz = self.dec_bwd(ctx, dz)
         dr2, _ = self.bn_join_bwd("bn2", dz, None, ACT_NONE, self.r2, self.co_c2)
         dyf = self.conv_bwd(self.c_c2, dr2)
         drf, _ = self.bn_join_bwd("bn_fusion", dyf, None, ACT_NONE, self.rf, self.co_fus)
@@ -1367,8 +1491,8 @@ class LateFusionPlan:
 
 
 class ModulePlan(LateFusionPlan):
-    """ONE BasicBlock (models.py:75-112), UpProjModule (models.py:181-209) or whole UpProj decoder (models.py:210-216: four modules in a
-    row) run through the very op builders the network plan uses (_block / _upproj and their backward), on a stand-alone NHWC input.
+    """ONE BasicBlock (models.py:75-112), UpProjModule (models.py:181-209) or whole UpProj / DeConv / UpConv decoder (models.py:115-216:
+    four layers in a row) run through the very op builders the network plan uses (_block / _upproj and their backward), on a stand-alone NHWC input.
     It backs the stand-alone `forward` of those modules (radar_depth_amd/model/models.py: the reference's sub-modules are callable on
     their own) and the layer-level parity tests against the reference-generated fixtures (tests/golden/upproj_module.npz,
     basic_block.npz).  owner: the ArenaOwner nn.Module whose gradient arena holds `mod`'s parameters (the module itself when it is
@@ -1384,7 +1508,7 @@ class ModulePlan(LateFusionPlan):
         self.x = self.act(self.N, self.H, self.W, self._cin)
         if self._kind == "decoder":
             mods = [("layer%d" % i, getattr(self._mod, "layer%d" % i)) for i in (1, 2, 3, 4)]
-            build, back = self._upproj, self._upproj_bwd
+            build, back = self._decoder_ops(self._mod)
         else:
             mods = [("m", self._mod)]
             build, back = (self._upproj, self._upproj_bwd) if self._kind == "upproj" else (self._block, self._block_bwd)

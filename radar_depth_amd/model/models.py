@@ -1,19 +1,19 @@
 """MI355X-native counterpart of the reference's model/models.py (hot-path subset).
 
-Same public surface -- Unpool, weights_init*, BasicBlock, Decoder, UpProj, choose_decoder,
+Same public surface -- Unpool, weights_init*, BasicBlock, Decoder, DeConv, UpConv, UpProj, choose_decoder,
 ResNet_latefusion with the reference's constructor signatures, attribute names and state_dict keys
-(/root/reference/model/models.py:13-27,30-72,75-133,178-230,519-664) -- but the arithmetic runs in
+(model/models.py:13-27,30-72,75-230,519-664) -- but the arithmetic runs in
 hand-written HIP kernels through the C ABI (include/radar_depth_hip.h):
 
-  * the child nn.Conv2d / nn.BatchNorm2d objects are parameter containers (OIHW weights, BN affine and
+  * the child nn.Conv2d / nn.ConvTranspose2d / nn.BatchNorm2d objects are parameter containers (OIHW weights, BN affine and
     running statistics) so that checkpoints, `weights_init`-style initialisers and optimizers see exactly
     the reference's tensors;
   * `ResNet_latefusion.forward` runs a static plan (radar_depth_amd/engine.py) of HIP kernels and is
     differentiable through torch.autograd (`loss.backward()` fills `.grad` of every parameter);
   * there is NO CPU / PyTorch fallback: calling forward on a CPU tensor or without the built library raises.
 
-Out of scope here (other --arch/--decoder choices of the reference): ResNet, ResNet_pnp, ResNet2,
-ResNet_multifusion, DeConv, UpConv; `choose_decoder` rejects them.
+Out of scope here (other --arch choices of the reference): ResNet, ResNet_pnp, ResNet2, ResNet_multifusion.  Of the
+decoders, DeConv serves kernel sizes 2 and 3 (`deconv2`, `deconv3`); `choose_decoder` raises NotImplementedError for larger ones.
 """
 import math
 import os
@@ -36,6 +36,18 @@ class _PlanOnly(nn.Module):
     def forward(self, *args, **kwargs):
         raise RuntimeError("%s is a parameter container: its arithmetic runs inside the parent network's HIP plan "
                            "(call the ResNet_latefusion / ResNet_multistage module)" % type(self).__name__)
+
+
+class ConvTranspose2d(nn.ConvTranspose2d):
+    """Plan-only nn.ConvTranspose2d: the weight [Cin, Cout, k, k] of a DeConv layer.  A subclass of nn.ConvTranspose2d, so that
+    isinstance-based initialisers (weights_init) and optimizers see what they see in the reference; its arithmetic runs in the
+    plan (engine.py: the adjoint convolution's descriptors, convdesc.deconv_*)."""
+    forward = _PlanOnly.forward
+
+
+def _convt(cin, cout, k):
+    """The reference's DeConv layer (models.py:122-133): stride 2, pad (k-1)//2, output_padding k%2 -- exactly 2x upsampling."""
+    return ConvTranspose2d(cin, cout, k, 2, (k - 1) // 2, k % 2, bias=False)
 
 
 class Unpool(nn.Module):
@@ -64,13 +76,18 @@ def weights_init(m):
         m.weight.data.normal_(0, math.sqrt(2.0 / fan))
         if m.bias is not None:
             m.bias.data.zero_()
+    elif isinstance(m, nn.ConvTranspose2d):
+        fan = m.kernel_size[0] * m.kernel_size[1] * m.in_channels
+        m.weight.data.normal_(0, math.sqrt(2.0 / fan))
+        if m.bias is not None:
+            m.bias.data.zero_()
     elif isinstance(m, nn.BatchNorm2d):
         m.weight.data.fill_(1)
         m.bias.data.zero_()
 
 
 def _kaiming(m, nonlin):
-    if isinstance(m, nn.Conv2d):
+    if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
         nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity=nonlin)
         if m.bias is not None:
             m.bias.data.zero_()
@@ -292,8 +309,56 @@ class Decoder(_PlanOnly):
         self.layer1 = self.layer2 = self.layer3 = self.layer4 = None
 
 
+class DeConv(_StandaloneForward, ArenaOwner, Decoder):
+    """Four ConvTranspose2d(k, stride 2) -> BatchNorm -> ReLU layers (models.py:115-146).  The plan runs each transposed convolution
+    as the adjoint of Conv2d(k, stride 2, pad (k-1)//2) (convdesc.deconv_*); kernel sizes 2 and 3."""
+    _plan_kind = "decoder"
+    _layer_kind = "deconv"
+
+    def __init__(self, in_channels, kernel_size):
+        assert kernel_size >= 2, "kernel_size out of range: {}".format(kernel_size)
+        super().__init__()
+
+        def convt(in_channels):
+            stride, padding, output_padding = 2, (kernel_size - 1) // 2, kernel_size % 2
+            assert -2 - 2 * padding + kernel_size + output_padding == 0, "deconv parameters incorrect"
+            return nn.Sequential(OrderedDict([
+                ("deconv{}".format(kernel_size), _convt(in_channels, in_channels // 2, kernel_size)),
+                ("batchnorm", nn.BatchNorm2d(in_channels // 2)),
+                ("relu", nn.ReLU(inplace=True)),
+            ]))
+
+        self.layer1 = convt(in_channels)
+        self.layer2 = convt(in_channels // 2)
+        self.layer3 = convt(in_channels // (2 ** 2))
+        self.layer4 = convt(in_channels // (2 ** 3))
+
+
+class UpConv(_StandaloneForward, ArenaOwner, Decoder):
+    """Four Unpool -> 5x5 conv -> BatchNorm -> ReLU layers (models.py:148-165): the UpProj bottom branch plus a ReLU, so the plan runs
+    the unpool folded into the 5x5 convolution (convdesc.upproj_fwd / upproj_dgrad with Cout = Cin/2)."""
+    _plan_kind = "decoder"
+    _layer_kind = "upconv"
+
+    def upconv_module(self, in_channels):
+        return nn.Sequential(OrderedDict([
+            ("unpool", Unpool(in_channels)),
+            ("conv", _conv(in_channels, in_channels // 2, 5)),
+            ("batchnorm", nn.BatchNorm2d(in_channels // 2)),
+            ("relu", nn.ReLU()),
+        ]))
+
+    def __init__(self, in_channels):
+        super().__init__()
+        self.layer1 = self.upconv_module(in_channels)
+        self.layer2 = self.upconv_module(in_channels // 2)
+        self.layer3 = self.upconv_module(in_channels // 4)
+        self.layer4 = self.upconv_module(in_channels // 8)
+
+
 class UpProj(_StandaloneForward, ArenaOwner, Decoder):
     _plan_kind = "decoder"
+    _layer_kind = "upproj"
 
     class UpProjModule(_StandaloneForward, ArenaOwner, _PlanOnly):
         _plan_kind = "upproj"
@@ -323,10 +388,22 @@ class UpProj(_StandaloneForward, ArenaOwner, Decoder):
         self.layer4 = self.UpProjModule(in_channels // 8)
 
 
+DECONV_KERNEL_SIZES = (2, 3)
+
+
 def choose_decoder(decoder, in_channels):
-    if decoder == "upproj":
+    if decoder[:6] == "deconv":
+        assert len(decoder) == 7
+        kernel_size = int(decoder[6])
+        if kernel_size > max(DECONV_KERNEL_SIZES):        # (kernel_size < 2: DeConv's own assertion, as in the reference)
+            raise NotImplementedError("decoder %s: the MI355X plan serves deconv2 and deconv3" % decoder)
+        return DeConv(in_channels, kernel_size)
+    elif decoder == "upproj":
         return UpProj(in_channels)
-    assert False, "invalid option for decoder: {}".format(decoder)
+    elif decoder == "upconv":
+        return UpConv(in_channels)
+    else:
+        assert False, "invalid option for decoder: {}".format(decoder)
 
 
 class ResNet_latefusion(ArenaOwner, nn.Module):

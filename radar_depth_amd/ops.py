@@ -77,6 +77,26 @@ def gconv_split(desc, x, w_split, out, bias=None, act=0, act_cols=0, addend=None
     return out
 
 
+def gemm_taps_split_supported(desc):
+    return lib().rd_gemm_taps_split_supported(C.byref(desc)) == 1
+
+
+def gemm_taps_split_stat_tiles(desc):
+    n = lib().rd_gemm_taps_split_stat_tiles(C.byref(desc))
+    if n < 0:
+        check(n, "rd_gemm_taps_split_stat_tiles")
+    return n
+
+
+def gemm_taps_split(desc, x, w_split, out, bias=None, act=0, act_cols=0, addend=None, ld_add=0, stat=None):
+    """rd_gconv_split's contract for descriptors whose phases have 1..4 taps, on the channel-grouped kernel (csrc/gemm_taps_split.hip)."""
+    _poison()
+    assert w_split.dtype == torch.bfloat16 and w_split.shape[0] == 3
+    check(lib().rd_gemm_taps_split(C.byref(desc), ptr(_f32(x)), ptr(w_split), C.c_int64(w_split[0].numel()), ptr(_f32(out)), ptr(bias), act,
+                                   act_cols, ptr(addend), ld_add, ptr(stat), current_stream()), "rd_gemm_taps_split")
+    return out
+
+
 def split_pieces(x_nhwc):
     """fp32 NHWC tensor -> three bf16 piece planes [3][C/16][M][16] (rd_split_pieces; x = p0 + p1 + p2 exactly)."""
     import torch
