@@ -303,11 +303,12 @@ int rd_pack_weights_batched(const void* jobs_dev, const int32_t* block_job_dev, 
 
 /* ---------------------------------------------------------------------------------------
  * Stem convolutions: 7x7 stride 2 pad 3 read straight from the network's NCHW input
- * (models.py:539,559,633,643; multistage_model.py:163-164,236-241).  The Cin (1..3) input
+ * (models.py:246,285 -- the early-fusion ResNet's stem, 1, 3 or 4 planes -> 64 channels --, 539,559,633,643;
+ * multistage_model.py:163-164,236-241).  The Cin (1..4; four planes with Cout = 64 only; rd_stem_fwd_bf16: 1..3) input
  * channels are given as separate planes: planes[i] points at image 0 of channel i ([H,W] each),
  * strides[i] is the element distance between consecutive images (Ctot*H*W for a channel of the
  * network input, H*W for a stand-alone map such as the stage-1 prediction).  Both arrays live in
- * host memory and are copied at call time.  Weights are packed [49][Cin][Cout]
+ * host memory, are read for i < Cin only and are copied at call time.  Weights are packed [49][Cin][Cout]
  * (rd_pack_weights).  Output NHWC [N,Ho,Wo,Cout], Ho = (H-1)/2+1.
  * ------------------------------------------------------------------------------------- */
 int rd_stem_fwd(const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H,
@@ -343,7 +344,8 @@ int rd_stem_wgrad(const float* const* planes, const int64_t* strides, int32_t Ci
  * fp32 dout are split into three bf16 pieces while they are staged, six v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation
  * (rd_gconv_split's arithmetic; a bf16 dout is its own single piece).  rd_stem_wgrad_t's contract: dtype is the element type of dout,
  * grad_oihw [Cout,Cin,7,7] is overwritten, ws needs rd_stem_wgrad_workspace_floats floats.  rd_stem_wgrad_split_supported: 1 for the
- * stems of the path (3 -> 64, 1 -> 16, 2 -> 16).  As close to an fp64 gradient as the fp32-MFMA kernel (tests/test_gpu_stem.py).
+ * stems of the path (3 -> 64, 1 -> 16, 2 -> 16; and, with an fp32 dout only, the early-fusion stems 4 -> 64 and 1 -> 64).  As close to
+ * an fp64 gradient as the fp32-MFMA kernel (tests/test_gpu_stem.py, tests/test_gpu_stem4.py).
  * (reference: loss.backward() through models.py:627-631 conv1 / conv1_depth, main.py:440) */
 int rd_stem_wgrad_split_supported(int32_t Cin, int32_t Cout);
 int rd_stem_wgrad_split_t(int32_t dtype, const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H,
@@ -352,7 +354,8 @@ int rd_stem_wgrad_split_t(int32_t dtype, const float* const* planes, const int64
  * (the RGB stem; the depth stem outside the multistage network's second stage), whose BatchNorm input gradient only this kernel would
  * read.  g: gradient at the BatchNorm OUTPUT [N,Ho,Wo,Cout] (what rd_bnact_maxpool_bwd_stats_t stores); x: the stem's raw output;
  * red_partial / n_tiles: that call's partial sums; coef_ws: 3*Cout floats.  Equivalent to rd_bn_bwd_apply_t(g, x, ..., which = 1, dx)
- * followed by rd_stem_wgrad_split_t(dx): same dgamma / dbeta, same weight-gradient bits, no dx tensor (3 -> 64 and 1 -> 16 stems). */
+ * followed by rd_stem_wgrad_split_t(dx): same dgamma / dbeta, same weight-gradient bits, no dx tensor (3 -> 64 and 1 -> 16 stems;
+ * fp32 tensors: 4 -> 64 and 1 -> 64 too). */
 int rd_stem_wgrad_split_bn_t(int32_t dtype, const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H,
                              int32_t W, const void* g, const void* x, const float* red_partial, int32_t n_tiles, const float* gamma,
                              const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef_ws, int32_t Cout,

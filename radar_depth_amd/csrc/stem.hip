@@ -13,8 +13,8 @@ int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, 
                        int O, int I, int co_off, int accumulate, hipStream_t s);
 
 struct StemArgs {
-    const float* plane[3];
-    long long stride[3];  // elements between consecutive images of each plane
+    const float* plane[4];
+    long long stride[4];  // elements between consecutive images of each plane
     const float* w;       // packed [49][Cin][Cout]
     const void* dout;     // wgrad: NHWC [N,Ho,Wo,Cout], fp32 or (io16) bf16
     void* out;            // forward: NHWC [N,Ho,Wo,Cout], fp32 or (io16) bf16
@@ -29,7 +29,9 @@ struct StemArgs {
 constexpr int ST_TW = 32;
 constexpr int ST_PW = 2 * ST_TW + 5;  // 69
 
-template <int NT>
+// NP: plane slots of the patch prefetch registers (3 for the one- to three-plane stems, 4 for the four-plane early-fusion stem: the
+// instantiations of the former are what they were before the latter existed)
+template <int NT, int NP = 3>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
     constexpr int TH = 8, PH = 2 * TH + 5, BN = NT * 32, MT = 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -87,13 +89,13 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
         ppx[u] = (short)px;
         prel[u] = py * a.W + px;
     }
-    auto fetch_patch = [&](int bid_, float (&v)[3][UP]) {
+    auto fetch_patch = [&](int bid_, float (&v)[NP][UP]) {
         const int n_ = bid_ / (a.tiles_h * a.tiles_w);
         const int trem_ = bid_ - n_ * (a.tiles_h * a.tiles_w);
         const int ih0_ = 2 * (trem_ / a.tiles_w) * TH - 3, iw0_ = 2 * (trem_ % a.tiles_w) * ST_TW - 3;
         const int org = ih0_ * a.W + iw0_;
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci) {
+        for (int ci = 0; ci < NP; ++ci) {
             if (ci < a.Cin) {
                 const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<float*>(a.plane[ci] + (size_t)n_ * a.stride[ci]), 0, (unsigned)(a.H * a.W) * 4u, 0x00020000);
@@ -106,7 +108,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
             }
         }
     };
-    float vnext[3][UP];
+    float vnext[NP][UP];
     if ((int)blockIdx.x < total_tiles) fetch_patch(blockIdx.x, vnext);
     for (int bid = blockIdx.x; bid < total_tiles; bid += gridDim.x) {
     const int n = bid / (a.tiles_h * a.tiles_w);
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
     rd_sync();          // the previous tile's MFMAs are done with the patch (and its statistics with s_red)
     if (!((a.debug & 1) && bid != (int)blockIdx.x)) {
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci)
+        for (int ci = 0; ci < NP; ++ci)
             if (ci < a.Cin) {
 #pragma unroll
                 for (int u = 0; u < UP; ++u)
@@ -263,8 +265,9 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemArgs a) {
 }
 
 // wgrad: D[k][co] += sum_pixels patch(k, pixel) * dout[pixel][co];  MTK = ceil(K/32) row tiles
-template <int MTK, int NT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void stem_wgrad_kernel(const StemArgs a, float* __restrict__ slabs) {
+// (MTK = 7, the four-plane stem: 224 accumulator registers per lane -- one wave per SIMD, the whole 512-register file)
+template <int MTK, int NT, int NP = 3>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MTK > 5 ? 1 : 2))) void stem_wgrad_kernel(const StemArgs a, float* __restrict__ slabs) {
     constexpr int TH = 4, PH = 2 * TH + 5, BN = NT * 32, NPIX = TH * ST_TW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
@@ -306,12 +309,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
         const int py = e / ST_PW, px = e - py * ST_PW;
         pyx[u] = ((e < PLANE ? py : 30000) << 16) | px;
     }
-    auto fetch_patch = [&](int tile_, float (&v)[3][UPW]) {
+    auto fetch_patch = [&](int tile_, float (&v)[NP][UPW]) {
         const int n_ = tile_ / (a.tiles_h * a.tiles_w);
         const int trem_ = tile_ - n_ * (a.tiles_h * a.tiles_w);
         const int ih0_ = 2 * (trem_ / a.tiles_w) * TH - 3, iw0_ = 2 * (trem_ % a.tiles_w) * ST_TW - 3;
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci) {
+        for (int ci = 0; ci < NP; ++ci) {
             if (ci < a.Cin) {
                 const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<float*>(a.plane[ci] + (size_t)n_ * a.stride[ci]), 0, (unsigned)(a.H * a.W) * 4u, 0x00020000);
@@ -324,7 +327,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
             }
         }
     };
-    float vnext[3][UPW];
+    float vnext[NP][UPW];
     if (tile_begin < tile_end) fetch_patch(tile_begin, vnext);
     for (int tile = tile_begin; tile < tile_end; ++tile) {
         const int n = tile / (a.tiles_h * a.tiles_w);
@@ -333,7 +336,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
         rd_sync();
         constexpr int U = 8;
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci)
+        for (int ci = 0; ci < NP; ++ci)
             if (ci < a.Cin) {
 #pragma unroll
                 for (int u = 0; u < UPW; ++u)
@@ -516,9 +519,9 @@ __global__ __launch_bounds__(256) void stem_dgrad_channel16_kernel(const T* __re
 }
 
 static int stem_fill(StemArgs& a, const float* const* planes, const int64_t* strides, int Cin, int N, int H, int W, int Cout) {
-    RD_CHECK_ARG(planes && strides && Cin >= 1 && Cin <= 3 && N > 0 && H > 6 && W > 6, "stem: bad arguments");
+    RD_CHECK_ARG(planes && strides && Cin >= 1 && Cin <= 4 && N > 0 && H > 6 && W > 6, "stem: bad arguments");
     RD_CHECK_ARG(Cout == 64 || Cout == 16 || Cout == 32, "stem: Cout=%d unsupported", Cout);
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 4; ++i) {
         a.plane[i] = i < Cin ? planes[i] : nullptr;
         a.stride[i] = i < Cin ? strides[i] : 0;
         RD_CHECK_ARG(i >= Cin || planes[i], "stem: null plane %d", i);
@@ -566,10 +569,14 @@ static int stem_fwd_impl(int io16, const float* const* planes, const int64_t* st
     const int Kq = Kp + 4;
     const size_t lds = ((size_t)((Kq + 3) & ~3) + (size_t)Kq * BN + (size_t)Cin * 21 * ST_PW + (size_t)8 * BN) * 4;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static std::atomic<unsigned long long> attr{0}, attr1{0};
+    static std::atomic<unsigned long long> attr{0}, attr1{0}, attr4{0};
     RD_SET_ATTR_ONCE(attr, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     RD_SET_ATTR_ONCE(attr1, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    if (NT == 2) hipLaunchKernelGGL(stem_fwd_kernel<2>, dim3(grid), dim3(256), lds, s, a);
+    RD_CHECK_ARG(Cin <= 3 || NT == 2, "stem_fwd: the four-plane stem has 64 output channels (Cout=%d)", Cout);
+    if (Cin == 4) {
+        RD_SET_ATTR_ONCE(attr4, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        hipLaunchKernelGGL((stem_fwd_kernel<2, 4>), dim3(grid), dim3(256), lds, s, a);
+    } else if (NT == 2) hipLaunchKernelGGL(stem_fwd_kernel<2>, dim3(grid), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(stem_fwd_kernel<1>, dim3(grid), dim3(256), lds, s, a);
     RD_CHECK_LAUNCH("stem_fwd_kernel");
     return RD_OK;
@@ -619,7 +626,11 @@ static int stem_wgrad_impl(int io16, const float* const* planes, const int64_t* 
         hipLaunchKernelGGL((stem_wgrad_kernel<M_, N_>), dim3(n_splits), dim3(256), lds, s, a, ws); \
         RD_CHECK_LAUNCH("stem_wgrad_kernel");                                                     \
     } else
-    RD_SW(5, 2) RD_SW(2, 1) RD_SW(4, 1) {
+    if (Cin == 4 && MTK == 7 && NT == 2) {
+        hipLaunchKernelGGL((stem_wgrad_kernel<7, 2, 4>), dim3(n_splits), dim3(256), lds, s, a, ws);
+        RD_CHECK_LAUNCH("stem_wgrad_kernel");
+    } else
+    RD_SW(5, 2) RD_SW(2, 1) RD_SW(4, 1) RD_SW(2, 2) {
         set_error("stem_wgrad: unsupported shape Cin=%d Cout=%d", Cin, Cout);
         return RD_EINVAL;
     }

@@ -1,4 +1,4 @@
-// fp32 stem convolution on the bf16 matrix cores (7x7, stride 2, pad 3, Cin = 1..3 planes of the NCHW network input -> NHWC
+// fp32 stem convolution on the bf16 matrix cores (7x7, stride 2, pad 3, Cin = 1..4 planes of the NCHW network input -> NHWC
 // [N,Ho,Wo,Cout]; models.py:539,559,633,643): the split plans' form of rd_stem_fwd.  Input and weights are split into three bf16
 // pieces while they are staged (x = x0 + x1 + x2 exactly, gconv_split.hip) and every product is rebuilt from six
 // v_mfma_f32_32x32x16_bf16 with fp32 accumulation: fp32 arithmetic at 2.67x the fp32 MFMA rate.
@@ -25,8 +25,8 @@ typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int su32x4 __attribute__((ext_vector_type(4)));
 
 struct StemSpArgs {
-    const float* plane[3];
-    long long stride[3];  // elements between consecutive images of each plane
+    const float* plane[4];
+    long long stride[4];  // elements between consecutive images of each plane
     const float* w;       // packed fp32 [49][Cin][Cout]
     float* out;           // NHWC [N,Ho,Wo,Cout]
     float* stat;
@@ -38,7 +38,9 @@ struct StemSpArgs {
 constexpr int SS_TH = 8, SS_TW = 32;
 constexpr int SS_PH = 2 * SS_TH + 5;         // 21 patch rows
 constexpr int SS_PW = 72;                    // staged patch columns (2*32 + 5 = 69 needed, 2*31 + 8 = 70 read)
-constexpr int SS_PPL = 3 * SS_PH * SS_PW;    // ushorts per piece plane of a patch buffer (9072 B: a multiple of 16)
+// ushorts per piece plane of a patch buffer: three plane slots for the one- to three-plane stems (9072 B), four for the four-plane
+// early-fusion stem (12096 B); both multiples of 16 bytes
+constexpr int ss_ppl(int cin) { return (cin > 3 ? cin : 3) * SS_PH * SS_PW; }
 
 // f(integral_constant<int, S>) for S = S0 .. ksteps-1: an unrolled loop whose index is a constant expression inside the body
 template <int S, int N, typename F>
@@ -54,6 +56,8 @@ __device__ __forceinline__ void static_steps(F&& f) {
 template <int NT, int CIN, int DBG>
 __global__ __launch_bounds__(512) void stem_fwd_split_kernel(const StemSpArgs a) {
     constexpr int BN = NT * 32, MT = 2;
+    constexpr int NP = CIN > 3 ? CIN : 3;      // plane slots
+    constexpr int SS_PPL = ss_ppl(CIN);
     extern __shared__ __attribute__((aligned(16))) unsigned short ssm[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
     const bool loader = wave >= 4;
@@ -101,9 +105,9 @@ __global__ __launch_bounds__(512) void stem_fwd_split_kernel(const StemSpArgs a)
         auto stage = [&](int tile_, int buf) {
             const int n_ = tile_ / tiles_img, trem_ = tile_ - n_ * tiles_img;
             const int ih0_ = 2 * (trem_ / a.tiles_w) * SS_TH - 3, iw0_ = 2 * (trem_ % a.tiles_w) * SS_TW - 3;
-            float f[3][UPB];
+            float f[NP][UPB];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < NP; ++c) {
                 if (c < CIN) {
                     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
                         const_cast<float*>(a.plane[c] + (size_t)n_ * a.stride[c]), 0, (unsigned)(a.H * a.W) * 4u, 0x00020000);
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(512) void stem_fwd_split_kernel(const StemSpArgs a)
             if (a.dbg & 2) return;
             unsigned short* pb = s_patch + (size_t)buf * 3 * SS_PPL;
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
+            for (int c = 0; c < NP; ++c)
                 if (c < CIN) {
 #pragma unroll
                     for (int q = 0; q < UPB; ++q) {
@@ -291,11 +295,11 @@ using namespace rd;
 
 extern "C" int rd_stem_fwd_split(const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H, int32_t W,
                                  const float* w_packed, int32_t Cout, float* out, float* stat_partial, void* stream) {
-    RD_CHECK_ARG(planes && strides && Cin >= 1 && Cin <= 3 && N > 0 && H > 6 && W > 6, "stem_split: bad arguments");
+    RD_CHECK_ARG(planes && strides && Cin >= 1 && Cin <= 4 && N > 0 && H > 6 && W > 6, "stem_split: bad arguments");
     RD_CHECK_ARG(Cout == 64 || Cout == 16 || Cout == 32, "stem_split: Cout=%d unsupported", Cout);
     RD_CHECK_ARG(w_packed && out, "stem_split: null tensor");
     StemSpArgs a;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 4; ++i) {
         a.plane[i] = i < Cin ? planes[i] : nullptr;
         a.stride[i] = i < Cin ? strides[i] : 0;
         RD_CHECK_ARG(i >= Cin || planes[i], "stem_split: null plane %d", i);
@@ -310,7 +314,9 @@ extern "C" int rd_stem_fwd_split(const float* const* planes, const int64_t* stri
     const int grid = total < num_cus() ? total : num_cus();      // one 8-wave workgroup per CU
     const int NT = Cout > 32 ? 2 : 1;
     const int ksteps = (Cin * 7 + 1) / 2;
-    const size_t lds = ((size_t)2 * 3 * SS_PPL + (size_t)3 * 2 * ksteps * NT * 32 * 8) * 2 + (size_t)4 * 2 * NT * 32 * sizeof(float);
+    // (four planes, 64 channels: 72 576 B of patch + 86 016 B of weights + 2 048 B = 160 640 B of the CU's 163 840 B)
+    RD_CHECK_ARG(Cin <= 3 || NT == 2, "stem_split: the four-plane stem has 64 output channels (Cout=%d)", Cout);
+    const size_t lds = ((size_t)2 * 3 * ss_ppl(Cin) + (size_t)3 * 2 * ksteps * NT * 32 * 8) * 2 + (size_t)4 * 2 * NT * 32 * sizeof(float);
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto launch = [&](auto k) -> int {
         static std::atomic<unsigned long long> attr_done{0};      // (one flag per instantiation of this generic lambda)
@@ -319,7 +325,8 @@ extern "C" int rd_stem_fwd_split(const float* const* planes, const int64_t* stri
         return RD_OK;
     };
     int rc;
-    if (NT == 2 && Cin == 3) rc = (dbg & 1) ? launch(stem_fwd_split_kernel<2, 3, 1>) : launch(stem_fwd_split_kernel<2, 3, 0>);
+    if (Cin == 4) rc = launch(stem_fwd_split_kernel<2, 4, 0>);
+    else if (NT == 2 && Cin == 3) rc = (dbg & 1) ? launch(stem_fwd_split_kernel<2, 3, 1>) : launch(stem_fwd_split_kernel<2, 3, 0>);
     else if (NT == 2) rc = Cin == 2 ? launch(stem_fwd_split_kernel<2, 2, 0>) : launch(stem_fwd_split_kernel<2, 1, 0>);
     else rc = Cin == 3 ? launch(stem_fwd_split_kernel<1, 3, 0>) : Cin == 2 ? launch(stem_fwd_split_kernel<1, 2, 0>) : launch(stem_fwd_split_kernel<1, 1, 0>);
     if (rc != RD_OK) return rc;

@@ -19,6 +19,8 @@
 //               split, 16-byte stores) into the other LDS buffer; one barrier per tile.  Waves 0-3 walk tile i: the tile's eight
 //               16-pixel reduction steps are dealt to them two each (split-K inside the workgroup), every wave holds the whole
 //               160 x 64 accumulator block (MTK x NT tiles of 32 x 32) and the four are summed through LDS at the end.
+//               The four-plane stem (196 rows, MTK = 7) does not fit that form's registers: there the four waves own disjoint row
+//               tiles (2 / 2 / 2 / 1), each walks all eight steps, and nothing is summed across waves (OWN below).
 //   pixel tile: 4 rows x 32 columns of one image.
 //   split-K   : contiguous tile ranges per workgroup, slabs [split][k][Cout] with k = (kh * 7 + kw) * Cin + c -- stem.hip's layout,
 //               reduced by the same deterministic slab reduction.
@@ -42,14 +44,15 @@ constexpr int SW_R = 4, SW_TW = 32, SW_PIX = SW_R * SW_TW;       // 128 output p
 constexpr int SW_PR = 2 * SW_R + 5;                              // 13 patch rows
 constexpr int SW_PC = 72;                                        // staged patch columns x = 0 .. 71 (read: 1 .. 70)
 constexpr int SW_PITCH = 40;                                     // elements per (row, parity) line (36 used)
-constexpr int SW_PPLANE = ((3 * SW_PR * 2 * SW_PITCH * 2 + 255) / 256) * 256;   // bytes of one piece of the patch (three input planes)
-constexpr int SW_XBYTES = 3 * SW_PPLANE;
+// bytes of one piece of the patch: three plane slots for the one- to three-plane stems, four for the four-plane early-fusion stem
+constexpr int sw_pplane(int cin) { return (((cin > 3 ? cin : 3) * SW_PR * 2 * SW_PITCH * 2 + 255) / 256) * 256; }
 constexpr int SW_YPLANE = SW_PIX * 64;                           // bytes of one [pixel][32 channels] bf16 plane of dout
 constexpr unsigned SW_OOB = 0x80000000u;
+constexpr int SW_FOLD = 4;                                       // (owned-tile form) tiles per inner accumulation chain
 
 struct StemWsArgs {
-    const float* plane[3];
-    long long stride[3];        // elements between consecutive images of each input plane
+    const float* plane[4];
+    long long stride[4];        // elements between consecutive images of each input plane
     const void* dout;           // NHWC [N,Ho,Wo,Cout], fp32 or (io16) bf16
     float* slabs;
     int Cin, N, H, W, Ho, Wo, Cout, tiles_h, tiles_w, total_tiles, tiles_per_split;
@@ -117,10 +120,19 @@ __device__ __forceinline__ swbf16x8 sw_row_finish(const unsigned (&e)[5], unsign
 // coefficients) by the staging waves
 template <int MTK, int NT, bool B16, bool BNF = false>
 __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs a) {
+    constexpr int CIN = MTK == 7 ? 4 : MTK == 5 ? 3 : MTK == 4 ? 2 : 1;      // (49 Cin rows in MTK tiles of 32)
+    constexpr int NPL = CIN > 3 ? CIN : 3;              // plane slots
+    constexpr int SW_PPLANE = sw_pplane(CIN), SW_XBYTES = 3 * SW_PPLANE;
     constexpr int YBYTES = 3 * NT * SW_YPLANE;          // (B16 plans use the first piece only)
     constexpr int BUF = SW_XBYTES + YBYTES;
     constexpr int NPB = B16 ? 1 : 3;
-    constexpr int CIN = MTK == 5 ? 3 : MTK == 4 ? 2 : 1;      // (49 Cin rows in MTK tiles of 32)
+    // OWN (the four-plane stem, MTK = 7): the whole MTK x NT block would be 224 accumulator registers per lane of the 256 an eight-wave
+    // workgroup leaves a wave.  The compute waves own DISJOINT row tiles instead (2 / 2 / 2 / 1) and each walks all eight reduction
+    // steps of a tile: 64 accumulator registers, no cross-wave sum at the end.  One accumulator then carries every pixel of the split
+    // (four times the chain of the other form, whose four partial blocks are summed at the end): the running block is folded into a
+    // second one every SW_FOLD tiles, which keeps the rounding of the long sum at the other form's level.
+    constexpr bool OWN = MTK > 5;
+    constexpr int MTA = OWN ? 2 : MTK;                  // row tiles a compute wave accumulates
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -134,7 +146,8 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
     const int ntiles = tile_end - tile_begin;
     const int tiles_img = a.tiles_h * a.tiles_w;
 
-    f32x16 acc[MTK][NT];      // (zeroed in the compute branch only)
+    f32x16 acc[MTA][NT];      // (zeroed in the compute branch only)
+    f32x16 accl[OWN ? MTA : 1][OWN ? NT : 1];      // (owned-tile form) the folded chains
 
     if (loader) {
         // ------------------------------------------------------------------------------------------ staging waves
@@ -161,7 +174,7 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
         const unsigned yimg = (unsigned)(a.Ho * a.Wo * a.Cout) * (B16 ? 2u : 4u);
         // two register sets: the loads of tile i + 2 are issued BEFORE tile i + 1 is split and stored, so that they have a whole iteration in
         // flight (with one set, issued behind the split, the next iteration's split waited for them: 195 us, 142 us without the loads)
-        struct Regs { float4 pf[3]; int pnval; float4 y0[UPY], y1[UPY]; float4 x0[BNF ? UPY : 1], x1[BNF ? UPY : 1]; unsigned ok; };
+        struct Regs { float4 pf[NPL]; int pnval; float4 y0[UPY], y1[UPY]; float4 x0[BNF ? UPY : 1], x1[BNF ? UPY : 1]; unsigned ok; };
         Regs ra, rb;
         ra.pnval = rb.pnval = 4;
         ra.ok = rb.ok = 0;
@@ -180,7 +193,7 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
             }
         }
         auto fetch = [&](int tile, Regs& rg) {
-            float4 (&pf)[3] = rg.pf; int& pnval = rg.pnval; float4 (&y0)[UPY] = rg.y0; float4 (&y1)[UPY] = rg.y1;
+            float4 (&pf)[NPL] = rg.pf; int& pnval = rg.pnval; float4 (&y0)[UPY] = rg.y0; float4 (&y1)[UPY] = rg.y1;
             if (a.dbg & 16) return;
             const int n = tile / tiles_img, tr = tile - n * tiles_img;
             const int r0 = (tr / a.tiles_w) * SW_R, c0 = (tr % a.tiles_w) * SW_TW;
@@ -190,7 +203,7 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
             pnval = nval;                                      // (the mask is applied when the values are split: nothing here may wait for a load)
             const unsigned poff = (pin && ih >= 0 && ih < a.H && iw >= 0 && nval > 0) ? (unsigned)(ih * a.W + iw) * 4u : SW_OOB;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < NPL; ++c) {
                 if (c < CIN) {
                     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
                         const_cast<float*>(a.plane[c] + (size_t)n * a.stride[c]), 0, (unsigned)(a.H * a.W) * 4u, 0x00020000);
@@ -224,10 +237,10 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
             rg.ok = okm;
         };
         auto split_put = [&](int buf, Regs& rg) {
-            float4 (&pf)[3] = rg.pf; const int pnval = rg.pnval; float4 (&y0)[UPY] = rg.y0; float4 (&y1)[UPY] = rg.y1;
+            float4 (&pf)[NPL] = rg.pf; const int pnval = rg.pnval; float4 (&y0)[UPY] = rg.y0; float4 (&y1)[UPY] = rg.y1;
             const unsigned base = lds0 + buf * BUF;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
+            for (int c = 0; c < NPL; ++c) {
                 if (c < CIN) {
                     // (columns past the right edge are the next row's first ones, or past the image: zero them)
                     float e0 = pf[c].x, e2 = pnval > 2 ? pf[c].z : 0.f, o0 = pnval > 1 ? pf[c].y : 0.f, o2 = pnval > 3 ? pf[c].w : 0.f;
@@ -326,17 +339,26 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
     } else {
         // ------------------------------------------------------------------------------------------ compute waves
 #pragma unroll
-        for (int mt = 0; mt < MTK; ++mt)
+        for (int mt = 0; mt < MTA; ++mt)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[mt][nt][i] = 0.f;
+        if constexpr (OWN) {
+#pragma unroll
+            for (int mt = 0; mt < MTA; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) accl[mt][nt][i] = 0.f;
+        }
         const int l31 = lane & 31, g = lane >> 5;
         // lane part of a patch fragment address: row m = mt * 32 + l31 = (kh * 7 + kw) * Cin + c; rows past K read row 0 (never stored)
-        unsigned arow[MTK], ash[MTK];
+        // (OWN: the wave's own row tiles MTA wave, MTA wave + 1)
+        unsigned arow[MTA], ash[MTA];
 #pragma unroll
-        for (int mt = 0; mt < MTK; ++mt) {
-            int m = mt * 32 + l31;
+        for (int mt = 0; mt < MTA; ++mt) {
+            int m = ((OWN ? MTA * wave : 0) + mt) * 32 + l31;
             if (m >= K) m = 0;
             const int t = m / CIN, c = m - t * CIN, kh = t / 7, kw = t - kh * 7;
             const int sh = (kw + 1) >> 1;
@@ -350,6 +372,76 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
             rd_sync();                            // B(i)
             if (a.dbg & 1) continue;
             const unsigned bo = (i & 1) * BUF;
+            if constexpr (OWN) {
+                // all eight reduction steps ks = (row ks >> 1, column half ks & 1) of the tile for this wave's row tiles.  The dout fragments
+                // of step ks + 1 are requested in front of step ks's MFMAs (two register sets), the patch rows as in the other form: the
+                // next row tile's dwords in front of this one's MFMAs, shifted into place behind them
+                const int nmt = min(MTA, MTK - MTA * wave);      // (wave-uniform: 2, 2, 2, 1)
+                auto xo_ = [&](int ks) { return bo + (unsigned)(4 * (ks >> 1) * SW_PITCH + 16 * (ks & 1)) * 2u; };
+                auto yo_ = [&](int ks) { return bo + (unsigned)((ks >> 1) * 32 + 16 * (ks & 1)) * 64u; };
+                unsigned R[3][5];
+                swbf16x8 A[3], B[2][NT][NPB];
+#pragma unroll
+                for (int p = 0; p < 3; ++p) sw_row_load(arow[0] + xo_(0) + p * SW_PPLANE, R[p]);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int p = 0; p < NPB; ++p) B[0][nt][p] = sw_frag_tr(yb + yo_(0) + nt * SW_YPLANE + p * NT * SW_YPLANE);
+#pragma unroll
+                for (int p = 0; p < 3; ++p) A[p] = sw_row_finish(R[p], ash[0]);
+#pragma unroll
+                for (int ks = 0; ks < 8; ++ks) {
+                    if (ks + 1 < 8) {
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                            for (int p = 0; p < NPB; ++p)
+                                B[(ks + 1) & 1][nt][p] = sw_frag_tr(yb + yo_(ks + 1) + nt * SW_YPLANE + p * NT * SW_YPLANE);
+                    }
+#pragma unroll
+                    for (int mt = 0; mt < MTA; ++mt) {
+                        const bool more = mt + 1 < MTA || ks + 1 < 8;
+                        const int nm = mt + 1 < MTA ? mt + 1 : 0, nks = mt + 1 < MTA ? ks : ks + 1;
+                        if (more) {
+#pragma unroll
+                            for (int p = 0; p < 3; ++p) sw_row_load(arow[nm] + xo_(nks) + p * SW_PPLANE, R[p]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (mt < nmt) {
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt) {
+                                f32x16 c = acc[mt][nt];
+                                if (B16) {
+                                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], B[ks & 1][nt][0], c, 0, 0, 0);
+                                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[ks & 1][nt][0], c, 0, 0, 0);
+                                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[ks & 1][nt][0], c, 0, 0, 0);
+                                } else {
+                                    RD_SPLIT_TERMS(c, A[0], A[1], A[2], B[ks & 1][nt][0], B[ks & 1][nt][NPB > 1 ? 1 : 0], B[ks & 1][nt][NPB > 2 ? 2 : 0])
+                                }
+                                acc[mt][nt] = c;
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (more) {
+#pragma unroll
+                            for (int p = 0; p < 3; ++p) A[p] = sw_row_finish(R[p], ash[nm]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                if ((i % SW_FOLD) == SW_FOLD - 1 || i + 1 == ntiles) {
+#pragma unroll
+                    for (int mt = 0; mt < MTA; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                            for (int e = 0; e < 16; ++e) {
+                                accl[mt][nt][e] += acc[mt][nt][e];
+                                acc[mt][nt][e] = 0.f;
+                            }
+                }
+                continue;
+            }
             // this wave's two reduction steps of the tile: ks = wave and wave + 4, step ks = (row ks >> 1, column half ks & 1)
             unsigned xo[2], yo[2];
 #pragma unroll
@@ -411,6 +503,22 @@ __global__ __launch_bounds__(512) void stem_wgrad_split_kernel(const StemWsArgs 
     float* red = smem;      // [4][16][64]
     float* slab = a.slabs + (size_t)split * K * a.Cout;
     const int l31 = lane & 31, hh = lane >> 5;
+    if constexpr (OWN) {
+        // every compute wave stores the row tiles it owns (accumulator register i of lane (hh, l31): row (i & 3) + 8 (i >> 2) + 4 hh, channel l31)
+        if (!loader) {
+#pragma unroll
+            for (int mt = 0; mt < MTA; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int k = (MTA * wave + mt) * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+                        const int co = nt * 32 + l31;
+                        if (k < K && co < a.Cout) slab[(size_t)k * a.Cout + co] = accl[mt][nt][i];
+                    }
+        }
+        return;
+    }
 #pragma unroll
     for (int mt = 0; mt < MTK; ++mt)
 #pragma unroll
@@ -443,7 +551,7 @@ extern "C" int64_t rd_stem_wgrad_workspace_floats(int32_t N, int32_t H, int32_t 
 extern "C" int rd_stem_wgrad_split_supported(int32_t Cin, int32_t Cout) {
     static const char* off = getenv("RD_STEM_WGRAD_SPLIT");      // RD_STEM_WGRAD_SPLIT=0: diagnostics
     if (off && atoi(off) == 0) return 0;
-    return ((Cin == 3 && Cout == 64) || (Cin >= 1 && Cin <= 2 && Cout == 16)) ? 1 : 0;
+    return ((Cin == 3 && Cout == 64) || (Cin >= 1 && Cin <= 2 && Cout == 16) || ((Cin == 4 || Cin == 1) && Cout == 64)) ? 1 : 0;
 }
 
 namespace rd {
@@ -456,11 +564,11 @@ static int stem_wgrad_split_impl(int32_t dtype, const float* const* planes, cons
                                  const float* bn_coef, const float* bn_mean) {
     RD_CHECK_ARG(dtype == RD_DTYPE_F32 || dtype == RD_DTYPE_BF16, "stem_wgrad_split_t: bad dtype %d", dtype);
     RD_CHECK_ARG(planes && strides && dout && grad_oihw && ws && N > 0 && H > 0 && W > 0, "stem_wgrad_split: null tensor / empty shape");
-    RD_CHECK_ARG(rd_stem_wgrad_split_supported(Cin, Cout) == 1 && cdiv(49 * Cin, 32) == (Cin == 3 ? 5 : Cin == 2 ? 4 : 2), "stem_wgrad_split: unsupported shape Cin=%d Cout=%d", Cin, Cout);
+    RD_CHECK_ARG(rd_stem_wgrad_split_supported(Cin, Cout) == 1 && cdiv(49 * Cin, 32) == (Cin == 4 ? 7 : Cin == 3 ? 5 : Cin == 2 ? 4 : 2), "stem_wgrad_split: unsupported shape Cin=%d Cout=%d", Cin, Cout);
     RD_CHECK_ARG((int64_t)H * W * 4 < (int64_t)SW_OOB && (int64_t)((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * Cout * 4 < (int64_t)SW_OOB,
                  "stem_wgrad_split: an image exceeds the 2 GB buffer-addressing range");
     StemWsArgs a;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < 4; ++c) {
         a.plane[c] = c < Cin ? planes[c] : nullptr;
         a.stride[c] = c < Cin ? strides[c] : 0;
         RD_CHECK_ARG(c >= Cin || planes[c] != nullptr, "stem_wgrad_split: null input plane %d", c);
@@ -486,7 +594,7 @@ static int stem_wgrad_split_impl(int32_t dtype, const float* const* planes, cons
     const int MTK = cdiv(K, 32), NT = Cout > 32 ? 2 : 1;
     const bool b16 = dtype == RD_DTYPE_BF16;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t lds = 2 * ((size_t)SW_XBYTES + 3 * (size_t)NT * SW_YPLANE);
+    const size_t lds = 2 * ((size_t)3 * sw_pplane(Cin) + 3 * (size_t)NT * SW_YPLANE);      // (four planes: 2 x (3 x 8 448 + 49 152) = 148 992 B)
     const bool bnf = bn_x != nullptr;
 #define RD_SWS(M_, N_, B_, F_)                                                                                       \
     if (MTK == M_ && NT == N_ && b16 == B_ && bnf == F_) {                                                           \
@@ -496,7 +604,8 @@ static int stem_wgrad_split_impl(int32_t dtype, const float* const* planes, cons
         RD_CHECK_LAUNCH("stem_wgrad_split_kernel");                                                                  \
     } else
     RD_SWS(5, 2, false, false) RD_SWS(5, 2, true, false) RD_SWS(2, 1, false, false) RD_SWS(2, 1, true, false) RD_SWS(4, 1, false, false)
-    RD_SWS(4, 1, true, false) RD_SWS(5, 2, false, true) RD_SWS(5, 2, true, true) RD_SWS(2, 1, false, true) RD_SWS(2, 1, true, true) {
+    RD_SWS(4, 1, true, false) RD_SWS(5, 2, false, true) RD_SWS(5, 2, true, true) RD_SWS(2, 1, false, true) RD_SWS(2, 1, true, true)
+    RD_SWS(7, 2, false, false) RD_SWS(7, 2, false, true) RD_SWS(2, 2, false, false) RD_SWS(2, 2, false, true) {
         set_error("stem_wgrad_split: no instantiation for Cin=%d Cout=%d%s", Cin, Cout, bnf ? " with the BatchNorm apply pass folded in" : "");
         return RD_EINVAL;
     }
@@ -515,7 +624,7 @@ extern "C" int rd_stem_wgrad_split_t(int32_t dtype, const float* const* planes, 
 // read: a read of g and x and a write of dx (1.1 GB at b = 16, the last kernel of the main chain) disappear.  g: gradient at the
 // BatchNorm OUTPUT (what rd_bnact_maxpool_bwd_stats_t stores); x: the stem's raw output; red_partial / n_tiles: that call's sums;
 // coef_ws: 3 * Cout floats.  Equivalent to rd_bn_bwd_apply_t(g, x, ..., which = 1, dx) + rd_stem_wgrad_split_t(dx): same dgamma / dbeta,
-// same weight-gradient bits (tests/test_gpu_stem.py).  Shapes: 3 -> 64 and 1 -> 16.
+// same weight-gradient bits (tests/test_gpu_stem.py, tests/test_gpu_stem4.py).  Shapes: 3 -> 64, 1 -> 16 and, fp32 tensors only, 4 -> 64 and 1 -> 64.
 extern "C" int rd_stem_wgrad_split_bn_t(int32_t dtype, const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H,
                                         int32_t W, const void* g, const void* x, const float* red_partial, int32_t n_tiles,
                                         const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,

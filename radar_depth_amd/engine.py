@@ -898,8 +898,9 @@ class LateFusionPlan:
         self.pack_jobs.append((conv.weight, wp, cout, cin, 49, cout, 0, cin, 0, None, 0))   # stem kernels read the plain layout
         tiles = self.L.rd_stem_stat_tiles(N, H, W)
         stat = self.buf(tiles, 2, cout) if self.train else None
-        pl = (C.c_void_p * 3)(*([p for p in planes] + [None] * (3 - len(planes))))
-        st = (C.c_int64 * 3)(*(list(strides) + [0] * (3 - len(strides))))
+        slots = max(3, len(planes))          # (the kernels read entries [0, cin) only; four for the early-fusion RGB-D stem)
+        pl = (C.c_void_p * slots)(*([p for p in planes] + [None] * (slots - len(planes))))
+        st = (C.c_int64 * slots)(*(list(strides) + [0] * (slots - len(strides))))
         self.keep += [pl, st]
         # bf16 plans: the 64-channel RGB stem forward runs on the bf16 matrix cores too (220 vs 574 us at b=16; its weight
         # gradient stays fp32); the 16-channel depth stem is faster on the fp32 kernel (175 vs 330 us)
@@ -1471,7 +1472,7 @@ class LateFusionPlan:
             self.bind_input(self.x_in.data_ptr(), self.x_in.shape[1])
 
     def run_forward(self, x=None):
-        """x: [N,>=4,H,W] fp32 CUDA tensor (copied into the plan's static input buffer) or None if already there."""
+        """x: [N,>=C,H,W] fp32 CUDA tensor, C the planes the network reads (copied into the plan's static input buffer) or None if already there."""
         self.set_stream()
         self.generation += 1
         self.bind_own_input()
@@ -1488,6 +1489,117 @@ class LateFusionPlan:
         if dpred is not None:
             self.dpred.copy_(dpred)
         self.run_list("bwd")
+
+
+class ResNetPlan(LateFusionPlan):
+    """The early-fusion network (models.py:233-303, ResNet.forward): ONE encoder on the network input's 1, 3 or 4 planes (modality d,
+    rgb, rgbd), conv2 / bn2 (no activation, models.py:295-296), decoder, head -- the late-fusion plan's op builders without a depth
+    stream and without the concat buffer.  Everything runs on the main stream, the weight-gradient chains on stream 2; stream 1 stays
+    idle (its segment joins are empty edges).  fp32 tensors with split or fp32 operands."""
+
+    def __init__(self, module, batch, height, width, train=True, dry_run=False, bf16=False, storage="fp32", segment_joins=True,
+                 autotune=None, split=False):
+        if bf16 or storage == "bf16":
+            raise NotImplementedError("the early-fusion ResNet plan serves fp32 tensors with split or fp32 operands: bf16 operands / "
+                                      "bf16 storage are outside its scope")
+        super().__init__(module, batch, height, width, train=train, dry_run=dry_run, segment_joins=segment_joins, autotune=autotune,
+                         split=split)
+
+    def _build(self):
+        m, N, H, W = self.m, self.N, self.H, self.W
+        hw = H * W
+        cin = m.conv1.weight.shape[1]
+        self.x_in = self.buf(N, cin, H, W)
+        xp = self.x_in.data_ptr()
+        self.probe(self.fwd, "fwd_begin", 0)
+        x, self.c_stem = self._stem("conv1", [xp + 4 * hw * c for c in range(cin)], [cin * hw] * cin, m.conv1, m.bn1, ACT_RELU, "maxpool")
+        self.x_bind = [(self.c_stem["pl"], self.c_stem["st"], 0, cin)]
+        self._x_bound = xp
+        self.pack_overlap = self.train and self.multi_stream and os.environ.get("RD_PACK_OVERLAP", "1") == "1"
+        if self.pack_overlap:
+            self.edge(self.fwd, "pack_join", 2, 0)
+        # the number of blocks per stage comes from the module: [2, 2, 2, 2] (resnet18) or [3, 4, 6, 3] (resnet34)
+        self.stages = []
+        for lname in ("layer1", "layer2", "layer3", "layer4"):
+            ctxs = []
+            for bi, blk in enumerate(getattr(m, lname)):
+                x, ctx = self._block("%s.%d" % (lname, bi), blk, x)
+                ctxs.append(ctx)
+            self.stages.append(ctxs)
+        self.probe(self.fwd, "fwd_encoder_end", 0)
+        dec_fwd, self.dec_bwd = self._decoder_ops(m.decoder)
+        dec_layers = (m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4)
+        if not self.train:
+            z = self.conv_bn_eval("conv2", x, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
+            self.taps["bn2"] = z
+            for i, mod in enumerate(dec_layers, 1):
+                z, _ = dec_fwd("decoder.layer%d" % i, mod, z)
+            self._head(z)
+            self._finish_pack_jobs()
+            return
+        self.r2, self.c_c2 = self.conv_fwd("conv2", x, [(m.conv2.weight, 0)], 1, 1, 0)
+        self.co_c2 = self.bn_coeffs("bn2", m.bn2, self.c_c2["stat"], self.c_c2["tiles"], self.r2.C, 0, self.r2.M)
+        z = self.bn_act("bn2", self.r2, self.co_c2, ACT_NONE)
+        self.ups = []
+        for i, mod in enumerate(dec_layers, 1):
+            z, ctx = dec_fwd("decoder.layer%d" % i, mod, z)
+            self.ups.append(ctx)
+        self._head(z)
+        self._finish_pack_jobs()
+        self._build_backward()
+
+    def _build_backward(self):
+        """Four bucket-aligned segments, each ending with the weight-gradient stream joined (self.bwd_segments):
+          0: head, decoder, bn2 / conv2     1: layer4     2: layer3     3: layer2, layer1, stem"""
+        m, N, z = self.m, self.N, self.z
+        self.dpred = self.buf(N, 1, self.Ho, self.Wo)
+        self.dx_dense = None
+        self.bwd_segments = []
+
+        def end_segment(prefixes, last=False):
+            evs = []
+            self._flush_reduces()
+            if last:
+                for q in (0, 2):
+                    self.probe(self.bwd, "bwd_end_stream%d" % q, q)
+            if last or self.segment_joins:
+                self.edge(self.bwd, "join2", 2, 0)
+            elif self.multi_stream and (self.stream_mask >> 1) & 1:
+                ev = self._event()
+                self.op(self.bwd, "segment_end2.record", self.L.rd_event_record, ev, self.streams[2])
+                evs.append(ev)
+            self.segment_events.append(evs)
+            begin = self.bwd_segments[-1][1] if self.bwd_segments else 0
+            self.bwd_segments.append((begin, len(self.bwd), prefixes))
+
+        ddm = self.buf(N, z.H, z.W)
+        self.op(self.bwd, "bilinear.bwd", self.L.rd_bilinear_bwd, _p(self.dpred), N, self.Ho, self.Wo, _p(ddm), z.H, z.W, self.stream)
+        dz = self.act(N, z.H, z.W, z.C)
+        ws = self.buf(int(self.L.rd_head_conv_bwd_workspace_floats(N, z.H, z.W, z.C)))
+        self.op(self.bwd, "conv3.dgrad", self.L.rd_head_conv_dgrad_t, self.dt, _p(m.conv3.weight), _p(ddm), N, z.H, z.W, z.C, dz.ptr, dz.ld,
+                self.stream)
+        fork = os.environ.get("RD_HEAD_WGRAD_FORK", "1") == "1"
+        if fork:
+            self.edge(self.bwd, "conv3.fork_wgrad", 0, 2)
+        with self.on(2 if fork else 0):
+            self.op(self.bwd, "conv3.wgrad", self.L.rd_head_conv_wgrad_t, self.dt, z.ptr, z.ld, _p(ddm), N, z.H, z.W, z.C,
+                    _p(self.grad_of(m.conv3.weight)), _p(ws), self.stream)
+        for ctx in reversed(self.ups):
+            dz = self.dec_bwd(ctx, dz)
+        dr2, _ = self.bn_join_bwd("bn2", dz, None, ACT_NONE, self.r2, self.co_c2)
+        g = self.conv_bwd(self.c_c2, dr2)
+        end_segment(("conv2", "bn2", "decoder", "conv3"))
+        self.probe(self.bwd, "bwd_encoder_begin", 0)
+        for stage in (3, 2):
+            for ctx in reversed(self.stages[stage]):
+                g = self._block_bwd(ctx, g)
+            end_segment(("layer%d" % (stage + 1),))
+        for stage in (1, 0):
+            for ctx in reversed(self.stages[stage]):
+                g = self._block_bwd(ctx, g)
+        # nobody asks an input gradient of this stem: on split plans its BatchNorm apply pass rides in the weight gradient's staging waves
+        self._stem_bwd(self.c_stem, g)
+        end_segment(("conv1", "bn1", "layer1", "layer2"), last=True)
 
 
 class ModulePlan(LateFusionPlan):

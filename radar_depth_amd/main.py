@@ -14,9 +14,9 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, lib, ptr
-from .model.models import ResNet_latefusion
+from .model.models import ResNet, ResNet_latefusion
 
-HOT_PATH_ARCHS = ("resnet18_latefusion", "resnet18_multistage", "resnet18_multistage_uncertainty_fixs")
+HOT_PATH_ARCHS = ("resnet18", "resnet34", "resnet18_latefusion", "resnet18_multistage", "resnet18_multistage_uncertainty_fixs")
 
 
 def create_model(args, output_size):
@@ -36,7 +36,11 @@ def create_model(args, output_size):
         model.register_parameter("w_stage1", w_stage1)
         model.register_parameter("w_stage2", w_stage2)
         return model, {"w_stage1": w_stage1, "w_stage2": w_stage2, "w_smooth": 0.1}
-    elif args.arch in ("resnet50", "resnet18", "resnet34", "resnet18_new", "resnet18_multistage_uncertainty"):
+    elif args.arch in ("resnet18", "resnet34"):
+        # the early-fusion baseline (main.py:126-131): one encoder on the modality's planes (rgb: 3, rgbd: 4, d: 1)
+        model = ResNet(layers=int(args.arch[6:]), decoder=args.decoder, output_size=output_size, in_channels=in_channels,
+                       pretrained=args.pretrained)
+    elif args.arch in ("resnet50", "resnet18_new", "resnet18_multistage_uncertainty"):
         raise NotImplementedError("--arch %s is outside the MI355X hot path (%s)" % (args.arch, ", ".join(HOT_PATH_ARCHS)))
     else:
         raise ValueError("[Error] Unknown model!!")
@@ -104,7 +108,7 @@ def unpack_buffers(bufs, flat):
 class HipTrainStep:
     """One reference training step entirely on the device (no host synchronisation inside):
 
-      resnet18_latefusion                    main.py:440-445   loss = MaskedL1(pred, target)
+      resnet18, resnet34, resnet18_latefusion  main.py:440-445   loss = MaskedL1(pred, target)
       resnet18_multistage                    main.py:431-438   loss = d1 + d2
       resnet18_multistage_uncertainty_fixs   main.py:416-429   loss = e^-w1 (d1 + 0.1 smooth) + e^-w2 d2 + w1 + w2
 
@@ -165,7 +169,7 @@ class HipTrainStep:
                                    split=operands == "split")
             self.plans = [self.mp.p1, self.mp.p2]
         else:
-            assert isinstance(model, ResNet_latefusion)
+            assert isinstance(model, (ResNet_latefusion, ResNet))
             self.mp = None
             self.plans = [model._plan(batch, height, width, True, bf16=operands == "bf16", storage=storage, segment_joins=joins,
                                       autotune=autotune, split=operands == "split")]
@@ -485,7 +489,7 @@ class HipTrainStep:
             pass
 
     def step(self, inputs, target):
-        """inputs [B,4,H,W], target [B,1,Ho,Wo] CUDA fp32.  Returns (loss[1], pred) device tensors (no sync).
+        """inputs [B,C,H,W] (C = 4, or the modality's 1 / 3 / 4 planes of the early-fusion ResNet), target [B,1,Ho,Wo] CUDA fp32.  Returns (loss[1], pred) device tensors (no sync).
         With comm="rccl" see synchronize_comm() before mixing in torch.distributed collectives."""
         caller = torch.cuda.current_stream()
         self.side.wait_stream(caller)
@@ -598,7 +602,7 @@ class HipInference:
         self._table.run()
 
     def __call__(self, x):
-        """x [B,>=4,H,W] CUDA fp32 -> prediction(s) (plan-owned tensors, valid until the next call)."""
+        """x [B,>=C,H,W] CUDA fp32 (C: the planes the network reads) -> prediction(s) (plan-owned tensors, valid until the next call)."""
         caller = torch.cuda.current_stream()
         self.side.wait_stream(caller)
         with torch.cuda.stream(self.side):

@@ -12,7 +12,8 @@ hand-written HIP kernels through the C ABI (include/radar_depth_hip.h):
     differentiable through torch.autograd (`loss.backward()` fills `.grad` of every parameter);
   * there is NO CPU / PyTorch fallback: calling forward on a CPU tensor or without the built library raises.
 
-Out of scope here (other --arch choices of the reference): ResNet, ResNet_pnp, ResNet2, ResNet_multifusion.  Of the
+ResNet (models.py:233-303) is the single-encoder, early-fusion network of `--arch resnet18 / resnet34` (modality rgb, rgbd or d).
+Out of scope here (other --arch choices of the reference): ResNet_pnp, ResNet2, ResNet_multifusion, the Bottleneck depths of ResNet.  Of the
 decoders, DeConv serves kernel sizes 2 and 3 (`deconv2`, `deconv3`); `choose_decoder` raises NotImplementedError for larger ones.
 """
 import math
@@ -493,6 +494,103 @@ class ResNet_latefusion(ArenaOwner, nn.Module):
         assert x.dim() == 4 and x.shape[1] >= 4
         x = x.contiguous().float()
         # (eval plans fold BatchNorm into the packed fp32 weights and run the fp32 kernels; training plans follow eager_operands())
+        plan = self._plan(x.shape[0], x.shape[2], x.shape[3], self.training, split=self.training and eager_operands(self) == "split")
+        if self.training and torch.is_grad_enabled():
+            return _PlanFunction.apply(plan, x, *self._arena_root()._ensure_arenas()["params"])
+        return plan.run_forward(x).clone()
+
+
+_BASIC_BLOCKS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
+
+
+class ResNet(ArenaOwner, nn.Module):
+    """The reference's early-fusion network (models.py:233-303): one ResNet-18 / ResNet-34 encoder on the 1, 3 or 4 input planes
+    (`len(modality)` for d, rgb, rgbd), conv2 / bn2, decoder, conv3, bilinear resize.  Same constructor, attribute names and
+    state_dict keys; the arithmetic runs in engine.ResNetPlan."""
+
+    def __init__(self, layers, decoder, output_size, in_channels=3, pretrained=True):
+        if layers not in _DEPTHS:
+            raise RuntimeError("Only 18, 34, 50, 101, and 152 layer model are defined for ResNet. Got {}".format(layers))
+        super().__init__()
+        if layers not in _BASIC_BLOCKS:
+            raise NotImplementedError("the MI355X hot path covers the BasicBlock depths of ResNet (layers=18, 34); the Bottleneck "
+                                      "depths (50, 101, 152) are outside its scope")
+        if in_channels not in (1, 3, 4):
+            raise NotImplementedError("the MI355X stem kernels read 1, 3 or 4 input planes (modality d, rgb, rgbd); got in_channels=%d"
+                                      % in_channels)
+        self.layers, self.in_channels = layers, in_channels
+        self.output_size = output_size
+        # the encoder as torchvision constructs it (Kaiming-normal fan_out on every convolution, BatchNorm 1 / 0), then -- pretrained --
+        # the ImageNet tensors; a stem that is not the RGB one is the reference's own (weights_init, models.py:246-249)
+        self.conv1 = _conv(3, 64, 7, 2)
+        self.bn1 = nn.BatchNorm2d(64)
+        weights_init_kaiming(self.conv1)
+        weights_init_kaiming(self.bn1)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        nb = _BASIC_BLOCKS[layers]
+        self.layer1 = _make_layer(64, 64, nb[0], 1, weights_init_kaiming)
+        self.layer2 = _make_layer(64, 128, nb[1], 2, weights_init_kaiming)
+        self.layer3 = _make_layer(128, 256, nb[2], 2, weights_init_kaiming)
+        self.layer4 = _make_layer(256, 512, nb[3], 2, weights_init_kaiming)
+        if pretrained:
+            self._load_imagenet_encoder()
+        if in_channels != 3:
+            self.conv1 = _conv(in_channels, 64, 7, 2)
+            self.bn1 = nn.BatchNorm2d(64)
+            weights_init(self.conv1)
+            weights_init(self.bn1)
+            # (re-assigning keeps the modules' places: conv1, bn1 stay first in state_dict and in the parameter arena)
+
+        self.conv2 = _conv(512, 256, 1, pad=0)
+        self.bn2 = nn.BatchNorm2d(256)
+        self.decoder = choose_decoder(decoder, 256)
+        self.conv3 = _conv(16, 1, 3)
+        self.bilinear = nn.Upsample(size=self.output_size, mode="bilinear", align_corners=True)
+
+        self.conv2.apply(weights_init)
+        self.bn2.apply(weights_init)
+        self.decoder.apply(weights_init)
+        self.conv3.apply(weights_init)
+        self.__dict__["_plans"] = {}
+        self._adopt_arena_children()
+
+    # the reference takes the encoder -- and, for three input planes, the stem (models.py:242-244) -- from
+    # torchvision.models.resnet{18,34}(pretrained=True); here they come from a local torchvision-format state_dict
+    def _load_imagenet_encoder(self):
+        var = "RADAR_DEPTH_RESNET%d_WEIGHTS" % self.layers
+        path = os.environ.get(var, "")
+        if not os.path.exists(path):
+            raise RuntimeError("pretrained=True needs ImageNet ResNet-%d weights: set %s to a torchvision resnet%d state_dict file, "
+                               "or construct with pretrained=False (--no-pretrain)" % (self.layers, var, self.layers))
+        sd = torch.load(path, map_location="cpu", weights_only=True)      # a plain torchvision state_dict: tensors only
+        own = self.state_dict()
+        tops = ("layer1", "layer2", "layer3", "layer4") + (("conv1", "bn1") if self.in_channels == 3 else ())
+        self.load_state_dict({k: v for k, v in sd.items() if k.split(".")[0] in tops and k in own}, strict=False)
+
+    # ------------------------------------------------------------------ HIP execution
+    def _plan(self, batch, height, width, train, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False):
+        from ..engine import ResNetPlan
+        if bf16 or storage == "bf16":
+            raise NotImplementedError("the early-fusion ResNet plan serves fp32 tensors with split or fp32 operands: bf16 operands / "
+                                      "bf16 storage are outside its scope")
+        st = self._ensure_arenas()
+        key = (batch, height, width, bool(train), st["version"], None, False, storage, bool(segment_joins), bool(split))
+        plans = self.__dict__.setdefault("_plans", {})
+        if key not in plans:
+            _evict_plans(plans, st["version"])
+            plans[key] = ResNetPlan(self, batch, height, width, train=train, segment_joins=segment_joins, autotune=autotune, split=split)
+        else:
+            plans[key] = plans.pop(key)          # most recently used last
+        return plans[key]
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("radar_depth_amd modules run on MI355X only (HIP kernels); got a %s tensor" % x.device.type)
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise RuntimeError("Given groups=1, weight of size %s, expected input%s to have %d channels, but got %d channels instead"
+                               % (list(self.conv1.weight.shape), list(x.shape), self.in_channels, x.shape[1] if x.dim() == 4 else -1))
+        x = x.contiguous().float()
         plan = self._plan(x.shape[0], x.shape[2], x.shape[3], self.training, split=self.training and eager_operands(self) == "split")
         if self.training and torch.is_grad_enabled():
             return _PlanFunction.apply(plan, x, *self._arena_root()._ensure_arenas()["params"])
