@@ -605,6 +605,9 @@ int rd_bnact_maxpool_fwd_t(int32_t dtype, const void* x, const float* scale, con
  * apart; pieces may be NULL = the plain kernel) -- the producers of the operands of rd_gconv_split_pre / rd_wgrad_split_pre: the split
  * arithmetic runs in these HBM-bound passes, where the VALU is idle, instead of in the staging waves of the MFMA-bound convolutions.
  * Same arguments as rd_bn_act / rd_bn_bwd_apply / rd_bn_bwd_apply_x / rd_bn_bwd_apply_x2 / rd_bnact_maxpool_fwd otherwise
+ * Plane arguments, checked alike by these five and by rd_split_pieces before anything is launched (RD_EINVAL): C % 16 == 0, pieces
+ * 16-byte aligned, piece_elems >= C * M and piece_elems % 8 == 0, M being the rows the launch writes (N * Ho * Wo pooled pixels for
+ * rd_bnact_maxpool_fwd_p).  A channel slice [c0, c0 + C) of a wider tensor passes pieces advanced by (c0 / 16) * M * 16 elements.
  * (models.py:96-112,203-208,633-650 and their backward). */
 int rd_bn_act_p(const float* x1, int32_t ldx1, const float* scale1, const float* shift1, const float* x2, int32_t ldx2, const float* scale2, const float* shift2, float* y, int32_t ldy, int64_t M, int32_t C, int32_t act, void* pieces, int64_t piece_elems, void* stream);
 int rd_bn_bwd_apply_p(const float* g, int32_t ldg, const float* x, int32_t ldx, const float* red_partial, int32_t n_tiles, int32_t which, const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef_ws, float* dx, int32_t lddx, int64_t M, int32_t C, void* pieces, int64_t piece_elems, void* stream);

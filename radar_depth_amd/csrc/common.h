@@ -100,6 +100,12 @@ struct AttrOnce {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// The one argument check of every producer of piece planes (rd_split_pieces and the _p entry points of norm_act.hip): M rows of C
+// channels into three planes piece_elems apart.  store_pieces4 writes 8-byte words, a consumer's global_load_lds copies 16-byte ones.
+static inline bool piece_planes_ok(const void* pieces, int64_t piece_elems, int64_t M, int C) {
+    return C >= 16 && C % 16 == 0 && M > 0 && reinterpret_cast<uintptr_t>(pieces) % 16 == 0 && piece_elems >= (int64_t)C * M &&
+           piece_elems % 8 == 0;
+}
 
 int num_cus();
 // conv16.hip: the 16 -> 16 channel 3x3 / stride-1 convolutions on the 16x16x4 fp32 MFMA (dispatched from gconv.hip's plans)

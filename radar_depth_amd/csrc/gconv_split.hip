@@ -1810,7 +1810,7 @@ __global__ __launch_bounds__(256) void split_pieces_kernel(const float* __restri
 
 extern "C" int rd_split_pieces(const float* x, int32_t ldx, int64_t M, int32_t C, void* pieces, int64_t piece_elems, void* stream) {
     RD_CHECK_ARG(x && pieces && M > 0 && C >= 16 && C % 16 == 0 && ldx % 4 == 0, "split_pieces: bad arguments (C must be a multiple of 16)");
-    RD_CHECK_ARG(piece_elems >= (int64_t)C * M && piece_elems % 8 == 0, "split_pieces: piece stride too small");
+    RD_CHECK_ARG(piece_planes_ok(pieces, piece_elems, M, C), "split_pieces: bad piece planes (16-byte aligned, piece_elems >= C * M and a multiple of 8)");
     const int64_t total = M * (C / 4);
     int64_t g = cdiv64(total, 256);
     const int64_t cap = (int64_t)num_cus() * 8;

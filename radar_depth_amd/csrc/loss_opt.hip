@@ -129,6 +129,15 @@ __device__ __forceinline__ float edge_w(const float* __restrict__ img, int C, in
     return expf(-s / (float)C);
 }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+// Normalised depth of one pixel, rounded ONCE.  Left to itself the compiler contracts the product into the subtraction that follows:
+// fma(-p1, inv, d0) subtracts an unrounded product from a rounded one, so two EQUAL neighbours differed by d0's rounding error and a
+// tie -- every flat region of a prediction -- got a sign (+-w/count in the gradient) where the reference's |.|' is 0.  The empty asm
+// makes the rounded product a value of its own (HIP's __fmul_rn is a plain multiplication and contracts like one).
+__device__ __forceinline__ float norm_depth(float p, float inv) {
+    float r = p * inv;
+    asm volatile("" : "+v"(r));
+    return r;
+}
 
 // pass 2: q[n,y,x] = dL/d(dhat) ; partial sums (loss_x, loss_y, sum q*pred) per block
 __global__ __launch_bounds__(256) void smooth_main_kernel(const float* __restrict__ pred, const float* __restrict__ image, int N,
@@ -144,27 +153,27 @@ __global__ __launch_bounds__(256) void smooth_main_kernel(const float* __restric
     double lx = 0.0, ly = 0.0, tq = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hw; e += (int64_t)gridDim.x * blockDim.x) {
         const int y = (int)((unsigned)e / (unsigned)W), x = (int)((unsigned)e - (unsigned)y * (unsigned)W);   // (one image: e < 2^31, checked by the host)
-        const float d = p[e] * inv;
+        const float d = norm_depth(p[e], inv);
         float qq = 0.f;
         if (x + 1 < W) {
             const float w = edge_w(img, C, hw, e, e + 1);
-            const float diff = d - p[e + 1] * inv;
+            const float diff = d - norm_depth(p[e + 1], inv);
             lx += (double)(fabsf(diff) * w);
             qq += w * sgn(diff) * inx;
         }
         if (x > 0) {
             const float w = edge_w(img, C, hw, e - 1, e);
-            qq -= w * sgn(p[e - 1] * inv - d) * inx;
+            qq -= w * sgn(norm_depth(p[e - 1], inv) - d) * inx;
         }
         if (y + 1 < H) {
             const float w = edge_w(img, C, hw, e, e + W);
-            const float diff = d - p[e + W] * inv;
+            const float diff = d - norm_depth(p[e + W], inv);
             ly += (double)(fabsf(diff) * w);
             qq += w * sgn(diff) * iny;
         }
         if (y > 0) {
             const float w = edge_w(img, C, hw, e - W, e);
-            qq -= w * sgn(p[e - W] * inv - d) * iny;
+            qq -= w * sgn(norm_depth(p[e - W], inv) - d) * iny;
         }
         q[(size_t)n * hw + e] = qq;
         tq += (double)qq * (double)p[e];

@@ -590,7 +590,7 @@ static int rd_bn_act_T(const T* x1, int32_t ldx1, const float* scale1, const flo
                        void* pieces = nullptr, int64_t piece_elems = 0) {
     RD_CHECK_ARG(x1 && scale1 && shift1 && y && M > 0 && C % 4 == 0 && ldx1 % 4 == 0 && ldy % 4 == 0 && (!x2 || ldx2 % 4 == 0),
                  "bn_act: bad arguments");
-    RD_CHECK_ARG(!pieces || (C % 16 == 0 && piece_elems >= (int64_t)C * M && reinterpret_cast<uintptr_t>(pieces) % 16 == 0), "bn_act: bad piece planes");
+    RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_act: bad piece planes");
     hipLaunchKernelGGL((bn_act_kernel<T>), dim3(ew_grid(M * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), x1, ldx1,
                        scale1, shift1, x2, ldx2, scale2, shift2, y, ldy, M, C, act, static_cast<unsigned short*>(pieces), piece_elems);
     RD_CHECK_LAUNCH("bn_act_kernel");
@@ -599,7 +599,9 @@ static int rd_bn_act_T(const T* x1, int32_t ldx1, const float* scale1, const flo
 extern "C" int rd_bn_act(const float* x1, int32_t ldx1, const float* scale1, const float* shift1, const float* x2, int32_t ldx2, const float* scale2, const float* shift2, float* y, int32_t ldy, int64_t M, int32_t C, int32_t act, void* stream) {
     return rd_bn_act_T<float>(x1, ldx1, scale1, shift1, x2, ldx2, scale2, shift2, y, ldy, M, C, act, stream);
 }
-// + piece planes of y for the pre-split convolutions (include/radar_depth_hip.h, rd_split_pieces): pieces may be NULL
+// + piece planes of y for the pre-split convolutions (include/radar_depth_hip.h, rd_split_pieces): pieces may be NULL.  Every _p entry
+// point of this file checks its planes with piece_planes_ok (common.h) before it launches anything: C % 16 == 0, a 16-byte aligned
+// pointer, piece_elems >= C * M and piece_elems % 8 == 0, where M counts the rows the launch WRITES (pooled pixels for the stem).
 extern "C" int rd_bn_act_p(const float* x1, int32_t ldx1, const float* scale1, const float* shift1, const float* x2, int32_t ldx2, const float* scale2, const float* shift2, float* y, int32_t ldy, int64_t M, int32_t C, int32_t act, void* pieces, int64_t piece_elems, void* stream) {
     return rd_bn_act_T<float>(x1, ldx1, scale1, shift1, x2, ldx2, scale2, shift2, y, ldy, M, C, act, stream, pieces, piece_elems);
 }
@@ -674,7 +676,7 @@ static int rd_bn_bwd_apply_T(const T* g, int32_t ldg, const T* x, int32_t ldx, c
                              void* pieces = nullptr, int64_t piece_elems = 0) {
     RD_CHECK_ARG(g && x && red_partial && gamma && mean && invstd && coef_ws && dx && (which == 1 || which == 2) && M > 0 &&
                      C % 4 == 0, "bn_bwd_apply: bad arguments");
-    RD_CHECK_ARG(!pieces || (C % 16 == 0 && piece_elems >= (int64_t)C * M && reinterpret_cast<uintptr_t>(pieces) % 16 == 0), "bn_bwd_apply: bad piece planes");
+    RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_bwd_apply: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, which, (double)M, gamma, invstd,
                        dgamma, dbeta, coef_ws);
@@ -721,7 +723,7 @@ static int rd_bn_bwd_apply_x2_T(const T* dy, int32_t lddy, const T* x1, int32_t 
                                 void* pieces1 = nullptr, int64_t piece_elems1 = 0, void* pieces2 = nullptr, int64_t piece_elems2 = 0) {
     RD_CHECK_ARG(dy && x1 && x2 && red_partial && gamma1 && gamma2 && mean1 && mean2 && invstd1 && invstd2 && scale1 && shift1 && scale2 &&
                      shift2 && coef_ws6 && dx1 && dx2 && M > 0 && C % 4 == 0, "bn_bwd_apply_x2: bad arguments");
-    RD_CHECK_ARG((!pieces1 || (C % 16 == 0 && piece_elems1 >= (int64_t)C * M)) && (!pieces2 || (C % 16 == 0 && piece_elems2 >= (int64_t)C * M)), "bn_bwd_apply_x2: bad piece planes");
+    RD_CHECK_ARG((!pieces1 || piece_planes_ok(pieces1, piece_elems1, M, C)) && (!pieces2 || piece_planes_ok(pieces2, piece_elems2, M, C)), "bn_bwd_apply_x2: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, 1, (double)M, gamma1, invstd1, dgamma1, dbeta1,
                        coef_ws6);
@@ -755,7 +757,7 @@ static int rd_bn_bwd_apply_x_T(const T* dy, int32_t lddy, const T* x, int32_t ld
                                void* pieces = nullptr, int64_t piece_elems = 0) {
     RD_CHECK_ARG(dy && x && red_partial && gamma && mean && invstd && scale && shift && coef_ws && dx && M > 0 && C % 4 == 0,
                  "bn_bwd_apply_x: bad arguments");
-    RD_CHECK_ARG(!pieces || (C % 16 == 0 && piece_elems >= (int64_t)C * M && reinterpret_cast<uintptr_t>(pieces) % 16 == 0), "bn_bwd_apply_x: bad piece planes");
+    RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_bwd_apply_x: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, 1, (double)M, gamma, invstd, dgamma,
                        dbeta, coef_ws);
@@ -783,8 +785,8 @@ template <typename T>
 static int rd_bnact_maxpool_fwd_T(const T* x, const float* scale, const float* shift, int32_t act, int32_t N, int32_t H, int32_t W, int32_t C, T* y, int32_t ldy, uint8_t* idx, void* stream,
                                   void* pieces = nullptr, int64_t piece_elems = 0) {
     RD_CHECK_ARG(x && scale && shift && y && idx && C % 4 == 0 && ldy % 4 == 0, "bnact_maxpool_fwd: bad arguments");
-    RD_CHECK_ARG(!pieces || (C % 16 == 0 && reinterpret_cast<uintptr_t>(pieces) % 16 == 0), "bnact_maxpool_fwd: bad piece planes");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, (int64_t)N * Ho * Wo, C), "bnact_maxpool_fwd: bad piece planes");     // (planes are indexed by OUTPUT pixels)
     hipLaunchKernelGGL((bnact_maxpool_fwd_kernel<T>), dim3(ew_grid((int64_t)N * Ho * Wo * (C / 4))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, scale, shift, act, N, H, W, C, Ho, Wo, y, ldy, idx, static_cast<unsigned short*>(pieces), piece_elems);
     RD_CHECK_LAUNCH("bnact_maxpool_fwd_kernel");

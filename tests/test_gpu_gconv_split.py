@@ -192,11 +192,14 @@ def _build(h, w):
     return m.cuda()
 
 
-def test_split_step_matches_oracle():
+@pytest.mark.parametrize("pre", ["1", "0"])
+def test_split_step_matches_oracle(pre, monkeypatch):
     """HipTrainStep(operands="split") against the CPU oracle for 3 SGD steps, at the tolerances of the fp32 plan's own test
     (tests/test_gpu_model.py::test_fused_step_matches_oracle): loss 2e-3, parameter norms 5e-3, head weight 5e-3 -- and the first
-    step's prediction within the north-star 1e-3 of the oracle's forward map."""
+    step's prediction within the north-star 1e-3 of the oracle's forward map.  pre: RD_SPLIT_PRE, "1" = the producers write piece
+    planes (the default plan), "0" = the consumers split while staging; same bars for both."""
     import numpy as np
+    monkeypatch.setenv("RD_SPLIT_PRE", pre)
     from oracle.criteria import MaskedL1Loss as OL1
     from oracle.models import ResNet_latefusion as ORef
     from radar_depth_amd.main import HipTrainStep
