@@ -516,6 +516,41 @@ int rd_stage_frames(const uint8_t* rgb_hwc, const int16_t* lidar, const int16_t*
                     int32_t i0, int32_t j0, int32_t H, int32_t W, float max_depth, float* inputs_nchw4, float* labels,
                     void* stream);
 
+/* Training-input staging: the reference's transform_train (dataset/nuscenes_dataset_torch_new.py:237-412; transform_mode
+ * "sparse-to-dense", sparsifier "radar") on the same frame arrays, bit-identical to it for the same random draws:
+ *   depth  int16/256 -> / float32(scale) -> rotation (scipy.ndimage.rotate, order 0) -> Pillow NEAREST resize -> crop -> flip
+ *   rgb    rotation -> byte scaling by the rotated frame's min / max (scipy <= 1.2 imresize) -> Pillow BILINEAR resize on 8-bit
+ *          data -> crop -> flip -> ImageEnhance Brightness / Contrast / Color in the drawn order -> /255
+ *   inputs [B,4,ch,cw] = (rgb, radar with values > max_depth zeroed)  (RD_MODALITY_RGB: [B,3,ch,cw], radar may be NULL),
+ *   labels [B,1,ch,cw] = lidar.
+ * `frames` is a HOST array of B per-frame parameter records (they travel to the kernels as launch arguments, RD_STAGE_TRAIN_CHUNK
+ * frames per launch chain): rot = (m00, m01, off0, m10, m11, off1), source coordinate = (y*m00 + x*m01) + off0 in float64, matrix
+ * [[c, s], [-s, c]] of the angle in degrees and offset = centre - M centre, centre = ((H0-1)/2, (W0-1)/2); factor / order: the
+ * enhancers' factors indexed by enhancer (0 brightness, 1 contrast, 2 saturation) and the enhancer applied first, second, third.
+ * The resize tables are DEVICE arrays covering the crop window of each frame (rows h_start .. h_start+ch, columns w_start ..
+ * w_start+cw of the int(H0*scale) x int(W0*scale) frame, before the flip): near_y [B,ch] / near_x [B,cw] the NEAREST source index,
+ * bil_y [B,ch,4] / bil_x [B,cw,4] = (first source index, k0, k1, 0), Pillow's 22-bit BILINEAR coefficients (two taps at most for
+ * scale >= 1).  Table indices are clamped to the frame.  `workspace`: rd_stage_train_workspace_bytes bytes on the device, 16-byte
+ * aligned; no state survives the call.  Three launches per chain on `stream`, no host synchronisation, integer atomics only
+ * (deterministic).  Rejected with RD_EINVAL before anything reaches the GPU: null pointers, H0 < ch or W0 < cw, a scale below 1, a
+ * crop window outside the resized frame, a jitter order that is not a permutation of 0, 1, 2. */
+#define RD_STAGE_TRAIN_CHUNK 16
+#define RD_MODALITY_RGBD 0
+#define RD_MODALITY_RGB 1
+typedef struct RdStageTrainFrame {
+    double rot[6];
+    double scale;
+    float factor[3];
+    int32_t order[3];
+    int32_t h_start, w_start, flip;
+    int32_t pad_;
+} RdStageTrainFrame;
+int64_t rd_stage_train_workspace_bytes(int32_t B, int32_t H0, int32_t W0, int32_t ch, int32_t cw);
+int rd_stage_frames_train(const uint8_t* rgb_hwc, const int16_t* lidar, const int16_t* radar, int32_t B, int32_t H0, int32_t W0,
+                          int32_t ch, int32_t cw, const RdStageTrainFrame* frames, const int32_t* near_y, const int32_t* near_x,
+                          const int32_t* bil_y, const int32_t* bil_x, void* workspace, float max_depth, int32_t modality,
+                          float* inputs, float* labels, void* stream);
+
 /* NCHW [N,C,H,W] (channel c0..c0+C of Ctot) <-> NHWC helpers for module-level tests */
 int rd_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

@@ -37,6 +37,11 @@ class RdReduceJob(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class RdStageTrainFrame(C.Structure):
+    _fields_ = [("rot", C.c_double * 6), ("scale", C.c_double), ("factor", C.c_float * 3), ("order", C.c_int32 * 3),
+                ("h_start", C.c_int32), ("w_start", C.c_int32), ("flip", C.c_int32), ("pad_", C.c_int32)]
+
+
 class RadarDepthHipError(RuntimeError):
     pass
 
@@ -56,7 +61,7 @@ def lib():
         _lib.rd_last_error.restype = C.c_char_p
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
-                     "rd_wgrad_split_workspace_floats"):
+                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
     return _lib
