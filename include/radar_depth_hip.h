@@ -481,6 +481,25 @@ int rd_masked_l2_bwd(const float* pred, const float* target, int64_t n, const do
  * sums[10] = count, sum d^2, sum |d|, sum |log10 o - log10 t|, sum |d|/t, #(r<1.25), #(r<1.25^2), #(r<1.25^3),
  * sum (1/o-1/t)^2, sum |1/o-1/t| over pixels with target > 0.  ws: 10*rd_loss_tiles(n) doubles. */
 int rd_depth_metrics(const float* output, const float* target, int64_t n, float* ws, double* sums, void* stream);
+/* The loss pass with the metric sums riding along (one read of pred and target): sums[2] bit-identical to rd_masked_l1_sums /
+ * rd_masked_l2_sums, msums[10] as rd_depth_metrics lists them.  ws: 12*rd_loss_tiles(n) doubles. */
+int rd_masked_l1_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums,
+                              double* msums, void* stream);
+int rd_masked_l2_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums,
+                              double* msums, void* stream);
+/* The ten sums of rd_depth_metrics for every frame of a [frames,1,H,W] pair (hw = H*W): sums[frames][10]; a frame
+ * without a valid pixel gets zeros.  ws: rd_depth_metrics_frames_workspace_floats(frames, hw) floats, 8-byte aligned. */
+int64_t rd_depth_metrics_frames_workspace_floats(int32_t frames, int64_t hw);
+int rd_depth_metrics_frames(const float* output, const float* target, int32_t frames, int64_t hw, float* ws,
+                            double* sums, void* stream);
+/* Result + AverageMeter.update (evaluation/metrics.py:34-58,192-206) on the device, one launch.  Row r of sums[rows][10]
+ * with count c = sums[r][0] becomes mse = s1/c, rmse = sqrt(mse), mae = s2/c, lg10 = s3/c, absrel = s4/c,
+ * delta1..3 = s5..7/c, irmse = sqrt(s8/c), imae = s9/c in fp64 (c == 0: NaN in all ten) and is added, weighted by
+ * weights[r] (device doubles; NULL = 1), into every meter g < n_groups whose bit is set in groups[r] (device int32
+ * masks; NULL = bit 0): meter[n_groups][12] = count, the ten weighted sums in Result.update's order (irmse, imae, mse,
+ * rmse, mae, absrel, lg10, delta1, delta2, delta3), number of updates.  last[10] = the metrics of row rows-1. */
+int rd_meter_update(const double* sums, int32_t rows, const double* weights, const int32_t* groups,
+                    int32_t n_groups, double* meter, double* last, void* stream);
 /* SmoothnessLoss (:8-28) on pred [N,1,H,W] and image [N,C,H,W] (NCHW).  out[0] = loss.
  * ws: rd_smooth_workspace_floats(N,H,W) floats, 8-byte aligned; rd_smooth_bwd reuses what fwd left there. */
 int64_t rd_smooth_workspace_floats(int32_t N, int32_t H, int32_t W);

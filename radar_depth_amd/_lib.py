@@ -61,9 +61,18 @@ def lib():
         _lib.rd_last_error.restype = C.c_char_p
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
-                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes"):
+                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
+        # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
+        vp = C.c_void_p
+        for name, args in (("rd_masked_l1_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
+                           ("rd_masked_l2_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
+                           ("rd_depth_metrics_frames_workspace_floats", [C.c_int32, C.c_int64]),
+                           ("rd_depth_metrics_frames", [vp, vp, C.c_int32, C.c_int64, vp, vp, vp]),
+                           ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp])):
+            if hasattr(_lib, name):
+                getattr(_lib, name).argtypes = args
     return _lib
 
 

@@ -72,34 +72,148 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ p
 // ---------------------------------------------------------------- evaluation metrics (evaluation/metrics.py:34-58)
 // part[block][10]: count, sum d^2, sum |d|, sum |log10 o - log10 t|, sum |d|/t, #(r<1.25), #(r<1.25^2), #(r<1.25^3),
 // sum (1/o-1/t)^2, sum |1/o-1/t|   over pixels with t > 0, d = o - t, r = max(o/t, t/o)
+// the ten fp32 terms of one valid pixel (t > 0), added in fp64 -- ONE definition for every kernel that produces these sums
+__device__ __forceinline__ void metric_terms(float o, float t, double* acc) {
+    const float inv_ln10 = 0.4342944819032518f;
+    const float ad = fabsf(o - t);
+    acc[0] += 1.0;
+    acc[1] += (double)(ad * ad);
+    acc[2] += (double)ad;
+    acc[3] += (double)fabsf(logf(o) * inv_ln10 - logf(t) * inv_ln10);
+    acc[4] += (double)(ad / t);
+    const float r = fmaxf(o / t, t / o);
+    if (r < 1.25f) acc[5] += 1.0;
+    if (r < 1.25f * 1.25f) acc[6] += 1.0;
+    if (r < 1.25f * 1.25f * 1.25f) acc[7] += 1.0;
+    const float id = fabsf(1.f / o - 1.f / t);
+    acc[8] += (double)(id * id);
+    acc[9] += (double)id;
+}
+
 __global__ __launch_bounds__(256) void metrics_partial_kernel(const float* __restrict__ out, const float* __restrict__ target,
                                                               int64_t n, double* __restrict__ part) {
     __shared__ double sh[4];
     double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const float inv_ln10 = 0.4342944819032518f;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
         const float t = target[e];
-        if (t > 0.f) {
-            const float o = out[e];
-            const float ad = fabsf(o - t);
-            acc[0] += 1.0;
-            acc[1] += (double)(ad * ad);
-            acc[2] += (double)ad;
-            acc[3] += (double)fabsf(logf(o) * inv_ln10 - logf(t) * inv_ln10);
-            acc[4] += (double)(ad / t);
-            const float r = fmaxf(o / t, t / o);
-            if (r < 1.25f) acc[5] += 1.0;
-            if (r < 1.25f * 1.25f) acc[6] += 1.0;
-            if (r < 1.25f * 1.25f * 1.25f) acc[7] += 1.0;
-            const float id = fabsf(1.f / o - 1.f / t);
-            acc[8] += (double)(id * id);
-            acc[9] += (double)id;
-        }
+        if (t > 0.f) metric_terms(out[e], t, acc);
     }
     for (int k = 0; k < 10; ++k) {
         const double s = block_sum_d(acc[k], sh);
         if (threadIdx.x == 0) part[(size_t)blockIdx.x * 10 + k] = s;
     }
+}
+
+// The loss pass of the training step with the metric sums riding along: part[block][12] = the two loss sums of l1_partial_kernel<SQ>
+// (same grid, same per-thread element order, same block_sum_d: bit-identical), then the ten sums of metrics_partial_kernel.
+template <bool SQ>
+__global__ __launch_bounds__(256) void l1_metrics_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                                 int64_t n, double* __restrict__ part) {
+    __shared__ double sh[4];
+    double s = 0.0, c = 0.0;
+    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const float t = target[e];
+        if (t > 0.f) {
+            const float o = pred[e];
+            const float diff = t - o;
+            s += SQ ? (double)(diff * diff) : (double)fabsf(diff);
+            c += 1.0;
+            metric_terms(o, t, acc);
+        }
+    }
+    s = block_sum_d(s, sh);
+    c = block_sum_d(c, sh);
+    double* o = part + (size_t)blockIdx.x * 12;
+    if (threadIdx.x == 0) {
+        o[0] = s;
+        o[1] = c;
+    }
+    for (int k = 0; k < 10; ++k) {
+        const double v = block_sum_d(acc[k], sh);
+        if (threadIdx.x == 0) o[2 + k] = v;
+    }
+}
+// pair_final_kernel's sums (same thread stride, same block_sum_d) over part[block][na + nb], written to two places
+__global__ __launch_bounds__(256) void split_final_kernel(const double* __restrict__ part, int nblocks, int na, int nb,
+                                                          double* __restrict__ out_a, double* __restrict__ out_b) {
+    __shared__ double sh[4];
+    const int stride = na + nb;
+    for (int k = 0; k < stride; ++k) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += part[(size_t)i * stride + k];
+        s = block_sum_d(s, sh);
+        if (threadIdx.x == 0) {
+            if (k < na) out_a[k] = s;
+            else out_b[k - na] = s;
+        }
+    }
+}
+
+// per-frame metric sums: grid (blocks per frame, frames), part[frame][block][10]; each frame is reduced exactly as
+// metrics_partial_kernel reduces a tensor of hw elements (same blocks per frame, same element order)
+__global__ __launch_bounds__(256) void metrics_frames_partial_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                                     int64_t hw, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const float* o = out + (size_t)blockIdx.y * hw;
+    const float* tg = target + (size_t)blockIdx.y * hw;
+    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hw; e += (int64_t)gridDim.x * blockDim.x) {
+        const float t = tg[e];
+        if (t > 0.f) metric_terms(o[e], t, acc);
+    }
+    double* dst = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 10;
+    for (int k = 0; k < 10; ++k) {
+        const double s = block_sum_d(acc[k], sh);
+        if (threadIdx.x == 0) dst[k] = s;
+    }
+}
+__global__ __launch_bounds__(256) void metrics_frames_final_kernel(const double* __restrict__ part, int nb, double* __restrict__ sums) {
+    __shared__ double sh[4];
+    const double* p = part + (size_t)blockIdx.x * nb * 10;
+    for (int k = 0; k < 10; ++k) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nb; i += blockDim.x) s += p[(size_t)i * 10 + k];
+        s = block_sum_d(s, sh);
+        if (threadIdx.x == 0) sums[(size_t)blockIdx.x * 10 + k] = s;
+    }
+}
+
+// ---------------------------------------------------------------- device-resident AverageMeter (evaluation/metrics.py:179-216)
+// Metric k (0..9, the argument order of Result.update: irmse, imae, mse, rmse, mae, absrel, lg10, delta1..3) of one row of ten sums,
+// as Result.evaluate finalises it.  A row without a valid pixel (count 0) gives 0/0 = NaN in all ten, like the mean of an empty selection.
+__device__ __forceinline__ double meter_metric(const double* __restrict__ row, int k) {
+    const double c = row[0];
+    switch (k) {
+        case 0: return sqrt(row[8] / c);
+        case 1: return row[9] / c;
+        case 2: return row[1] / c;
+        case 3: return sqrt(row[1] / c);
+        case 4: return row[2] / c;
+        case 5: return row[4] / c;
+        case 6: return row[3] / c;
+        default: return row[k - 2] / c;       // delta1..3 = row[5..7]
+    }
+}
+// One workgroup, no atomics: thread (g, j) owns word j of meter g -- j = 0 the count, 1..10 the weighted metric sums, 11 the number of
+// updates -- and walks the rows in order; the first ten threads also keep the latest row's metrics.
+__global__ __launch_bounds__(256) void meter_update_kernel(const double* __restrict__ sums, int rows, const double* __restrict__ weights,
+                                                           const int32_t* __restrict__ groups, int n_groups, double* __restrict__ meter,
+                                                           double* __restrict__ last) {
+    for (int i = threadIdx.x; i < n_groups * 12; i += blockDim.x) {
+        const int g = i / 12, j = i - g * 12;
+        double v = meter[i];
+        for (int r = 0; r < rows; ++r) {
+            const int32_t mask = groups ? groups[r] : 1;
+            if (!((mask >> g) & 1)) continue;
+            const double w = weights ? weights[r] : 1.0;
+            if (j == 0) v += w;
+            else if (j == 11) v += 1.0;
+            else v += w * meter_metric(sums + (size_t)r * 10, j - 1);
+        }
+        meter[i] = v;
+    }
+    if (threadIdx.x < 10) last[threadIdx.x] = meter_metric(sums + (size_t)(rows - 1) * 10, threadIdx.x);
 }
 
 // ---------------------------------------------------------------- smoothness
@@ -330,6 +444,63 @@ extern "C" int rd_depth_metrics(const float* output, const float* target, int64_
     RD_CHECK_LAUNCH("metrics_partial_kernel");
     hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, s, part, g, 10, sums);
     RD_CHECK_LAUNCH("pair_final_kernel");
+    return RD_OK;
+}
+
+// Loss sums and metric sums in one pass over pred / target: sums[2] exactly as rd_masked_l1_sums / rd_masked_l2_sums write them,
+// msums[10] as rd_depth_metrics lists them.  ws: 12*rd_loss_tiles(n) doubles
+template <bool SQ>
+static int sums_metrics(const char* what, const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
+                        void* stream) {
+    RD_CHECK_ARG(pred && target && ws && sums && msums && n > 0 && ((uintptr_t)ws & 7) == 0, "%s: bad arguments", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int g = red_grid(n);
+    double* part = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(l1_metrics_partial_kernel<SQ>, dim3(g), dim3(256), 0, s, pred, target, n, part);
+    RD_CHECK_LAUNCH("l1_metrics_partial_kernel");
+    hipLaunchKernelGGL(split_final_kernel, dim3(1), dim3(256), 0, s, part, g, 2, 10, sums, msums);
+    RD_CHECK_LAUNCH("split_final_kernel");
+    return RD_OK;
+}
+extern "C" int rd_masked_l1_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
+                                         void* stream) {
+    return sums_metrics<false>("masked_l1_sums_metrics", pred, target, n, ws, sums, msums, stream);
+}
+extern "C" int rd_masked_l2_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
+                                         void* stream) {
+    return sums_metrics<true>("masked_l2_sums_metrics", pred, target, n, ws, sums, msums, stream);
+}
+
+// sums[frames][10]: the ten sums of rd_depth_metrics for every frame of a [frames,1,H,W] pair (hw = H*W); a frame without a valid
+// pixel gets a row of zeros.  ws: rd_depth_metrics_frames_workspace_floats(frames, hw) floats, 8-byte aligned
+extern "C" int64_t rd_depth_metrics_frames_workspace_floats(int32_t frames, int64_t hw) {
+    if (frames <= 0 || hw <= 0) return 0;
+    return 2 * (int64_t)frames * red_grid(hw) * 10;
+}
+extern "C" int rd_depth_metrics_frames(const float* output, const float* target, int32_t frames, int64_t hw, float* ws, double* sums,
+                                       void* stream) {
+    RD_CHECK_ARG(output && target && ws && sums && frames > 0 && hw > 0 && ((uintptr_t)ws & 7) == 0, "depth_metrics_frames: bad arguments");
+    RD_CHECK_ARG(frames <= 65535, "depth_metrics_frames: at most 65535 frames per call, got %d", frames);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int g = red_grid(hw);
+    double* part = reinterpret_cast<double*>(ws);
+    hipLaunchKernelGGL(metrics_frames_partial_kernel, dim3(g, frames), dim3(256), 0, s, output, target, hw, part);
+    RD_CHECK_LAUNCH("metrics_frames_partial_kernel");
+    hipLaunchKernelGGL(metrics_frames_final_kernel, dim3(frames), dim3(256), 0, s, part, g, sums);
+    RD_CHECK_LAUNCH("metrics_frames_final_kernel");
+    return RD_OK;
+}
+
+// Result + AverageMeter.update on the device: each of `rows` rows of ten sums becomes the ten metrics (fp64) and is added, weighted
+// by weights[row] (nullptr: 1), into every meter g < n_groups whose bit is set in groups[row] (nullptr: bit 0).
+// meter[n_groups][12] = count, ten weighted sums in Result.update's order, number of updates; last[10] = the latest row's metrics.
+extern "C" int rd_meter_update(const double* sums, int32_t rows, const double* weights, const int32_t* groups, int32_t n_groups,
+                               double* meter, double* last, void* stream) {
+    RD_CHECK_ARG(sums && meter && last && rows > 0, "meter_update: bad arguments");
+    RD_CHECK_ARG(n_groups >= 1 && n_groups <= 31, "meter_update: n_groups must be 1..31 (one bit of an int32 mask each), got %d", n_groups);
+    hipLaunchKernelGGL(meter_update_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), sums, rows, weights, groups,
+                       n_groups, meter, last);
+    RD_CHECK_LAUNCH("meter_update_kernel");
     return RD_OK;
 }
 

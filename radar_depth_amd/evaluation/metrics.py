@@ -86,3 +86,157 @@ class AverageMeter(object):
                    self.sum_absrel / c, self.sum_lg10 / c, self.sum_delta1 / c, self.sum_delta2 / c, self.sum_delta3 / c,
                    self.sum_gpu_time / c, self.sum_data_time / c)
         return avg
+
+
+def _result_from_metrics(values, gpu_time=0, data_time=0):
+    r = Result()
+    r.update(*[float(v) for v in values], gpu_time, data_time)
+    return r
+
+
+class DeviceAverageMeter(object):
+    """Result.evaluate + AverageMeter.update (evaluation/metrics.py:34-58, :192-206) without leaving the device: update() enqueues
+    the metric sums and one rd_meter_update launch on the current stream and returns; average() / last() do the only readback.
+    `groups` meters share one update (validate()'s day / night / rain meters, main.py:635-654): a frame goes to every meter whose
+    bit is set in its mask.
+
+    buf[groups][12] (float64): count, the ten weighted sums in Result.update's order, number of updates; last_buf[10]: the latest
+    Result.  Both persist for the life of the object (HipTrainStep's captured step writes them on every replay)."""
+
+    def __init__(self, groups=1, device=None):
+        if not 1 <= int(groups) <= 31:
+            raise ValueError("DeviceAverageMeter: groups must be 1..31 (one bit of an int32 mask each), got %r" % (groups,))
+        self.groups = int(groups)
+        self.device = None if device is None else torch.device(device)
+        self._buf = self._last_buf = None
+        self.sum_gpu_time, self.sum_data_time = 0, 0
+        self._ws = {}               # (frames, hw) -> (workspace, sums): reused by every update of that geometry
+        self._weights = {}          # weight -> one device double
+
+    def _alloc(self):
+        if self._buf is None:               # (on first use: constructing a meter needs no GPU)
+            if not torch.cuda.is_available():
+                raise RuntimeError("radar_depth_amd metrics run on MI355X only (HIP kernels)")
+            if self.device is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            self._buf = torch.zeros(self.groups, 12, dtype=torch.float64, device=self.device)
+            self._last_buf = torch.zeros(10, dtype=torch.float64, device=self.device)
+
+    @property
+    def buf(self):
+        self._alloc()
+        return self._buf
+
+    @property
+    def last_buf(self):
+        self._alloc()
+        return self._last_buf
+
+    def reset(self):
+        """Asynchronous: two fills on the current stream."""
+        if self._buf is not None:
+            self._buf.zero_()
+            self._last_buf.zero_()
+        self.sum_gpu_time, self.sum_data_time = 0, 0
+
+    def add_times(self, gpu_time, data_time, n=1):
+        """The host-side timings of AverageMeter.update (they never were device quantities)."""
+        self.sum_gpu_time += n * gpu_time
+        self.sum_data_time += n * data_time
+
+    def _weight(self, n):
+        w = self._weights.get(n)
+        if w is None:
+            w = self._weights[n] = torch.full((1,), float(n), dtype=torch.float64, device=self.device)
+        return w
+
+    def _group_masks(self, groups, frames):
+        if groups is None:
+            return None
+        if torch.is_tensor(groups):
+            if groups.dtype != torch.int32 or groups.numel() != frames:
+                raise ValueError("DeviceAverageMeter: groups must be %d int32 bitmasks" % frames)
+            return groups.to(self.device, non_blocking=True).contiguous()
+        masks = [int(g) for g in groups]
+        if len(masks) != frames or any(m < 0 or m >> self.groups for m in masks):
+            raise ValueError("DeviceAverageMeter: groups must be %d bitmasks over %d meters, got %r" % (frames, self.groups, masks))
+        return torch.tensor(masks, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+
+    def update(self, pred, target, n=None, per_frame=False, groups=None):
+        """per_frame=False: ONE Result over the whole tensor, weight n (default pred.size(0)) -- train()'s call (main.py:449-452).
+        per_frame=True: every frame of [B,1,H,W] is its own Result with weight 1 -- validate() at batch 1 (main.py:625-654);
+        groups: per-frame bitmasks (sequence, or int32 tensor: a device tensor costs no copy).  Never synchronises."""
+        if not (pred.is_cuda and target.is_cuda):
+            raise RuntimeError("radar_depth_amd metrics run on MI355X only (HIP kernels)")
+        if pred.shape != target.shape:
+            raise ValueError("DeviceAverageMeter: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+        L = lib()
+        self._alloc()
+        pred = pred.detach().contiguous().float()
+        target = target.detach().contiguous().float()
+        frames = pred.size(0) if per_frame else 1
+        hw = pred.numel() // frames
+        masks = self._group_masks(groups, frames) if per_frame else (None if groups is None else self._group_masks([groups], 1))
+        key = (frames, hw, per_frame)
+        if key not in self._ws:
+            nd = (int(L.rd_depth_metrics_frames_workspace_floats(frames, hw)) // 2 if per_frame else
+                  10 * L.rd_loss_tiles(C.c_int64(hw)))
+            self._ws[key] = (torch.empty(nd, dtype=torch.float64, device=self.device),
+                             torch.empty(frames, 10, dtype=torch.float64, device=self.device))
+        ws, sums = self._ws[key]
+        s = current_stream()
+        if per_frame:
+            check(L.rd_depth_metrics_frames(ptr(pred), ptr(target), frames, hw, ptr(ws), ptr(sums), s), "rd_depth_metrics_frames")
+            weights = None
+        else:
+            check(L.rd_depth_metrics(ptr(pred), ptr(target), C.c_int64(hw), ptr(ws), ptr(sums), s), "rd_depth_metrics")
+            weights = self._weight(pred.size(0) if n is None else n)
+        check(L.rd_meter_update(ptr(sums), frames, ptr(weights), ptr(masks), self.groups, ptr(self.buf), ptr(self.last_buf), s),
+              "rd_meter_update")
+
+    def count(self, group=0):
+        """Sum of the weights meter `group` has received (a readback)."""
+        return float(self.buf[group, 0].item())
+
+    def average(self, group=0):
+        m = self.buf[group].cpu().numpy()           # the only host synchronisation
+        c = float(m[0])
+        if c == 0:
+            raise ZeroDivisionError("float division by zero")       # AverageMeter.average() on an empty meter
+        return _result_from_metrics(m[1:11] / c, self.sum_gpu_time / c, self.sum_data_time / c)
+
+    def last(self):
+        return _result_from_metrics(self.last_buf.cpu().numpy())
+
+
+# validate()'s eight condition meters (main.py:546-562, :635-654) as bits of one DeviceAverageMeter(groups=9): bit 0 is
+# average_meter itself
+DAYNIGHT_GROUPS = ("all", "day", "night", "rain", "sun", "day_rain", "day_sun", "night_rain", "night_sun")
+
+
+def daynight_mask(daynight_info):
+    """Bitmask over DAYNIGHT_GROUPS of the meters that main.py:635-654 updates for one frame's `daynight_info` string."""
+    bit = {name: 1 << k for k, name in enumerate(DAYNIGHT_GROUPS)}
+    mask = bit["all"]
+    rain = "rain" in daynight_info
+    for time in ("day", "night"):
+        if time in daynight_info:
+            mask |= bit[time] | (bit["rain"] | bit[time + "_rain"] if rain else bit["sun"] | bit[time + "_sun"])
+    return mask
+
+
+def evaluate_batch(meter, preds, target, groups=None):
+    """Batched validation: every frame of a HipInference output is evaluated on its own and enters the meter(s) with weight 1, so
+    a batch of B frames leaves exactly what B passes of validate()'s batch-1 loop leave (main.py:625-654) -- one Result over the
+    whole batch would pool the frames by valid-pixel count instead.  preds: the prediction [B,1,H,W], or the multistage dict;
+    then `meter` may be a pair (average_meter, average_meter_stage1).  groups: per-frame bitmasks (see daynight_mask)."""
+    stage1 = None
+    if isinstance(meter, (tuple, list)):
+        meter, stage1 = meter
+    if isinstance(preds, dict):
+        if stage1 is not None:
+            stage1.update(preds["stage1"], target, per_frame=True, groups=groups)
+        preds = preds["stage2"]
+    elif stage1 is not None:
+        raise ValueError("evaluate_batch: a stage-1 meter needs the multistage prediction dict")
+    meter.update(preds, target, per_frame=True, groups=groups)

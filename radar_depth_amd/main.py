@@ -134,11 +134,15 @@ class HipTrainStep:
     fp32 tolerances unchanged; everything else is the fp32 path."""
 
     def __init__(self, model, batch, height, width, lr=0.01, momentum=0.9, weight_decay=1e-4, loss_weights=None, use_graph=False,
-                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None):
+                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None, metrics=False):
         """criterion: "l1" (MaskedL1Loss, the default of utils.parse_command) or "l2" (MaskedMSELoss, `-c l2`, main.py:294-305).
         comm: "rccl" = the C ABI's own communicator (radar_depth_amd.comm, rd_allreduce_bucket on a dedicated communication
         stream, event-chained behind each backward segment); "torch" = torch.distributed.all_reduce (the cross-check);
-        "auto" = rccl when radar_depth_amd.comm is initialised, else torch when torch.distributed is, else single-GPU."""
+        "auto" = rccl when radar_depth_amd.comm is initialised, else torch when torch.distributed is, else single-GPU.
+        metrics: keep the reference's per-step Result / AverageMeter bookkeeping (main.py:449-458) on the device: the loss pass also
+        produces the ten metric sums of the prediction and one small launch adds them, weighted by the batch size, into self.meter
+        (evaluation.metrics.DeviceAverageMeter; self.meter_stage1 for the multistage archs, per rank when data-parallel).  Nothing
+        is read back until meter.average() / meter.last() is called."""
         from .model.multistage_model import ResNet_multistage
         assert criterion in ("l1", "l2"), criterion
         # storage="bf16": NHWC activations and their gradients live in HBM as bf16 (implies bf16 conv operands); BatchNorm
@@ -220,6 +224,18 @@ class HipTrainStep:
                 self.w1, self.w2 = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
                 self.dw1, self.dw2 = torch.zeros(1, device=dev), torch.zeros(1, device=dev)
             self.loss = self.loss4[3:4]
+        self.metrics = bool(metrics)
+        self.meter, self.meter_stage1 = None, None
+        if self.metrics:
+            from .evaluation.metrics import DeviceAverageMeter
+            self._f_sums_metrics = self.L.rd_masked_l1_sums_metrics if criterion == "l1" else self.L.rd_masked_l2_sums_metrics
+            self.metrics_ws = torch.zeros(12 * tiles, dtype=torch.float64, device=dev)
+            self.meter = DeviceAverageMeter(device=dev)
+            self.meter_stage1 = DeviceAverageMeter(device=dev) if self.multistage else None
+            # per prediction tensor: (ten metric sums of the step, its meter); the meters' weight is the batch size (main.py:452)
+            self._meter_of = {id(pl.pred): (torch.zeros(10, dtype=torch.float64, device=dev), m)
+                              for pl, m in zip(self.plans[::-1], (self.meter, self.meter_stage1))}
+            self._meter_weight = torch.full((1,), float(batch), dtype=torch.float64, device=dev)
         self.use_graph = use_graph
         self.graphs = None
         self.steps = 0                 # optimizer steps (state_dict: a momentum state exists once > 0)
@@ -322,6 +338,12 @@ class HipTrainStep:
     # ---- pieces of one step: each is a list of (name, C-ABI function, arguments) on the step's streams, separately
     # ---- graph-capturable; after piece i (i < len(buckets)) the gradient bucket i is final
     def _l1_ops(self, tag, pred, sums, s):
+        if self.metrics:
+            msums, meter = self._meter_of[id(pred)]
+            return [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(self.metrics_ws),
+                                                                   ptr(sums), ptr(msums), s)),
+                    (tag + ".meter", self.L.rd_meter_update, (ptr(msums), 1, ptr(self._meter_weight), None, 1, ptr(meter.buf),
+                                                              ptr(meter.last_buf), s))]
         return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(self.l1_ws), ptr(sums), s))]
 
     def _l1_bwd_ops(self, tag, pred, sums, coef, dpred, accumulate, s):
