@@ -570,6 +570,60 @@ int rd_stage_frames_train(const uint8_t* rgb_hwc, const int16_t* lidar, const in
                           const int32_t* bil_y, const int32_t* bil_x, void* workspace, float max_depth, int32_t modality,
                           float* inputs, float* labels, void* stream);
 
+/* The radar_filtered sparsifier (csrc/radar_filter.hip): the reference's per-frame filter_radar_points
+ * (dataset/nuscenes_dataset_torch_new.py:557-584 -> filter_radar_points_gt, dataset/radar_preprocessing.py:77-122), the index_map it
+ * scatters, and the part of transform_val / transform_train that carries index_map along and zeroes the radar returns the filter
+ * rejected (same file :323-328, :335-348, :462-486), for a batch of frames with ragged point counts.  Points are padded device
+ * arrays; the counts n_radar[B] / n_lidar[B] are HOST arrays that travel as launch arguments (RD_STAGE_TRAIN_CHUNK frames per
+ * launch).  Nothing at or beyond a frame's count is ever read, so the padding may hold anything (NaN included).  No host
+ * synchronisation, no readback; the only atomics are the integer atomicMax of the scatter (order independent).
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_ERADAR_NULL      a null pointer
+ *   RD_ERADAR_RANGE     B, Rmax, Lmax or the frame size out of range (B 1..65536, Rmax 1..2^20, Lmax 1..2^24, H0*W0 < 2^30)
+ *   RD_ERADAR_NRADAR    n_radar[b] < 0 or > Rmax
+ *   RD_ERADAR_NLIDAR    n_lidar[b] < 0 or > Lmax
+ *   RD_ERADAR_FEWLIDAR  n_radar[b] > 0 with n_lidar[b] < 3: the reference cannot index three neighbours either
+ *   RD_ERADAR_CROP      the crop does not fit the frame (training: the window does not fit the resized frame, scale below 1)
+ * n_radar[b] == 0 is valid (the map is all -1, nothing is filtered).  n_radar[b] == 1 follows the same rule as any other count; the
+ * reference's np.squeeze drops the point axis there and its own code fails. */
+#define RD_ERADAR_NULL (-10)
+#define RD_ERADAR_RANGE (-11)
+#define RD_ERADAR_NRADAR (-12)
+#define RD_ERADAR_NLIDAR (-13)
+#define RD_ERADAR_FEWLIDAR (-14)
+#define RD_ERADAR_CROP (-15)
+/* filter_radar_points_gt.  radar_xy [B,Rmax,2], radar_depth [B,Rmax], lidar_xy [B,Lmax,2], lidar_depth [B,Lmax]: float64, 16-byte
+ * aligned.  Per radar point: the k = 3 nearest lidar points by (sqrt(dx*dx + dy*dy), lower index) in float64; c = how many of the
+ * three lie within exp(depth_j*dist_log/100 + dist_off) (a count over all three, not a prefix); of the FIRST c neighbours, how many
+ * pass the SIGNED test radar_depth - depth_j < exp(depth_j*depth_log/100 + depth_off); label 2 if c == 0, 1 if passes >= ceil(c/2),
+ * else 0; valid = label > 0.  thresholds = (dist_log, dist_off, depth_log, depth_off) = (log(4/14), log(14), log(16/5), log(5)) as
+ * the host's numpy computes them; only exp runs on the device.  labels / valid uint8 [B,Rmax], topk int32 [B,Rmax,3]; rows at or
+ * beyond n_radar[b] are written as label 0, valid 0, topk -1. */
+int rd_radar_filter_points(const double* radar_xy, const double* radar_depth, const double* lidar_xy, const double* lidar_depth,
+                           const int32_t* n_radar, const int32_t* n_lidar, int32_t B, int32_t Rmax, int32_t Lmax,
+                           const double* thresholds, uint8_t* labels, uint8_t* valid, int32_t* topk, void* stream);
+/* index_map int32 [B,H0,W0]: -1, then point i < n_radar[b] writes i at row (int)y, column (int)x (truncation toward zero, as
+ * astype(np.int32)); of several points in one pixel the highest index stays, which is what numpy's repeated-index assignment leaves.
+ * A point whose truncated coordinate lies outside the frame (or is NaN) is skipped; the reference wraps a negative index around and
+ * raises IndexError beyond the frame. */
+int rd_radar_index_map(const double* radar_xy, const int32_t* n_radar, int32_t B, int32_t Rmax, int32_t H0, int32_t W0,
+                       int32_t* index_map, void* stream);
+/* index_map through the transform of the depth maps, and the filter on the already staged inputs, one launch per chunk of frames:
+ *   index_map_out int32 [B,1,H,W]   the centre crop at (i0, j0) (val) / NEAREST tables -> order-0 rotation sample -> crop -> flip with
+ *                                   the records and tables of rd_stage_frames_train (train); no division by the scale; where the
+ *                                   rotation samples outside the frame the value is 0 (the reference's cval), not -1
+ *   inputs[b, 3, y, x] = 0          where apply_filter and the transformed index v has 0 <= v < n_radar[b] and valid[b, v] == 0.
+ * inputs is fp32 [B,4,H,W] as rd_stage_frames / rd_stage_frames_train left it (zeroing commutes with their max-depth clamp); it may
+ * be NULL when apply_filter == 0.  A rotation fill of 0 does match an invalid point 0, as in the reference.  index_map_out holds in
+ * int32 what the reference keeps as an int64 array and hands out, after its ToTensor, as float32. */
+int rd_stage_index_filter_val(const int32_t* index_map, const uint8_t* valid, const int32_t* n_radar, int32_t B, int32_t Rmax, int32_t H0,
+                              int32_t W0, int32_t i0, int32_t j0, int32_t H, int32_t W, int32_t apply_filter, float* inputs,
+                              int32_t* index_map_out, void* stream);
+int rd_stage_index_filter_train(const int32_t* index_map, const uint8_t* valid, const int32_t* n_radar, int32_t B, int32_t Rmax,
+                                int32_t H0, int32_t W0, int32_t ch, int32_t cw, const RdStageTrainFrame* frames, const int32_t* near_y,
+                                const int32_t* near_x, int32_t apply_filter, float* inputs, int32_t* index_map_out, void* stream);
+
 /* NCHW [N,C,H,W] (channel c0..c0+C of Ctot) <-> NHWC helpers for module-level tests */
 int rd_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

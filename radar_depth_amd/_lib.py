@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("RD_LIB_PATH") or os.path.join(HERE, "lib", "libradard
 RD_MAX_TAPS = 25
 RD_MAX_PHASES = 4
 ACT_NONE, ACT_RELU, ACT_LEAKY02 = 0, 1, 2
+# argument-check codes of the radar_filtered entry points (include/radar_depth_hip.h)
+RD_ERADAR_NULL, RD_ERADAR_RANGE, RD_ERADAR_NRADAR, RD_ERADAR_NLIDAR, RD_ERADAR_FEWLIDAR, RD_ERADAR_CROP = -10, -11, -12, -13, -14, -15
 
 
 class RdPhase(C.Structure):
@@ -70,7 +72,12 @@ def lib():
                            ("rd_masked_l2_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
                            ("rd_depth_metrics_frames_workspace_floats", [C.c_int32, C.c_int64]),
                            ("rd_depth_metrics_frames", [vp, vp, C.c_int32, C.c_int64, vp, vp, vp]),
-                           ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp])):
+                           ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
+                           # the radar_filtered sparsifier (csrc/radar_filter.hip)
+                           ("rd_radar_filter_points", [vp] * 6 + [C.c_int32] * 3 + [vp] * 5),
+                           ("rd_radar_index_map", [vp, vp] + [C.c_int32] * 4 + [vp, vp]),
+                           ("rd_stage_index_filter_val", [vp] * 3 + [C.c_int32] * 9 + [vp] * 3),
+                           ("rd_stage_index_filter_train", [vp] * 3 + [C.c_int32] * 6 + [vp] * 3 + [C.c_int32] + [vp] * 3)):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = args
     return _lib

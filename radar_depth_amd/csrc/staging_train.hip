@@ -22,7 +22,7 @@
 // come from host-built tables (IEEE division on the host, as numpy does it).  With scale >= 1 Pillow's bilinear filter has at most two
 // taps per axis, which is why the tables carry (first index, k0, k1).  Table indices are clamped to the frame before use, so a wrong
 // table gives wrong pixels, never an out-of-bounds read.
-#include "common.h"
+#include "staging_geom.h"      // kChunk, TrainFrames, rot_src, near_src (shared with radar_filter.hip)
 
 #include <algorithm>
 
@@ -30,21 +30,7 @@
 
 namespace rd {
 
-constexpr int kChunk = RD_STAGE_TRAIN_CHUNK;
-struct TrainFrames { RdStageTrainFrame f[kChunk]; };
 struct TrainLut { float v[256]; };
-
-// scipy.ndimage's order-0 sample of output pixel (y, x) of the rotation: the source index, or false where the reference writes cval = 0
-__device__ __forceinline__ bool rot_src(const double m00, const double m01, const double off0, const double m10, const double m11, const double off1,
-                                        int H0, int W0, int y, int x, int& iy, int& ix) {
-    const double fy = (double)y, fx = (double)x;
-    const double cy = (fy * m00 + fx * m01) + off0;
-    const double cx = (fy * m10 + fx * m11) + off1;
-    const bool ok = cy >= 0.0 && cy <= (double)(H0 - 1) && cx >= 0.0 && cx <= (double)(W0 - 1);      // false for NaN as well
-    iy = ok ? (int)floor(cy + 0.5) : 0;
-    ix = ok ? (int)floor(cx + 0.5) : 0;
-    return ok;
-}
 
 __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
@@ -208,7 +194,7 @@ __global__ __launch_bounds__(256) void train_finish_kernel(const int16_t* __rest
     const int W4 = (cw + 3) >> 2, n = ch * W4;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
         const int y = e / W4, x0 = (e - y * W4) * 4, nx = min(4, cw - x0);
-        const int sy = min(max(near_y[(int64_t)b * ch + y], 0), H0 - 1);
+        const int sy = near_src(near_y, b, ch, y, H0);
         float o[5][4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -220,7 +206,7 @@ __global__ __launch_bounds__(256) void train_finish_kernel(const int16_t* __rest
                 enhance1(o2, f2, mean, r, g, bb);
                 o[0][k] = s_lut[r]; o[1][k] = s_lut[g]; o[2][k] = s_lut[bb];
                 const int x = x0 + k;
-                const int sx = min(max(near_x[(int64_t)b * cw + (flip ? cw - 1 - x : x)], 0), W0 - 1);
+                const int sx = near_src(near_x, b, cw, flip ? cw - 1 - x : x, W0);
                 int iy, ix;
                 const bool ok = rot_src(m00, m01, off0, m10, m11, off1, H0, W0, sy, sx, iy, ix);
                 const int64_t idx = (int64_t)iy * W0 + ix;

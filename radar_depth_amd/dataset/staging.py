@@ -8,7 +8,15 @@ Mirrors the deterministic part of the reference's DataLoader worker -- ``nuscene
 therefore the decoded arrays (``np.array(f[key])``, :186-188).  There is no CPU fallback.
 
 The second half of the file is the training input: ``transform_train`` (same file :237-412) with its random rotation, scale, crop,
-flip and colour jitter, bit-identical for the same draws (``draw_train_params``, ``stage_train_batch``; ``rd_stage_frames_train``)."""
+flip and colour jitter, bit-identical for the same draws (``draw_train_params``, ``stage_train_batch``; ``rd_stage_frames_train``).
+
+Between the two sits the ``radar_filtered`` sparsifier: ``filter_radar_points`` restates what the reference's ``__getitem__`` does to
+every frame (same file :557-584 and ``filter_radar_points_gt``, dataset/radar_preprocessing.py:77-122) for a padded batch of radar and
+lidar points -- per-point labels, ``valid_mask``, the dense ``index_map`` -- and both staging calls take its result
+(``sparsifier="radar_filtered", radar_filter=..., extras=...``): ``index_map`` follows the depth maps through the transform and the radar
+returns the filter rejected are zeroed, equal to the reference's output for the same frames, points and draws
+(``rd_radar_filter_points``, ``rd_radar_index_map``, ``rd_stage_index_filter_val`` / ``_train``).  ``uniform`` and ``lidar_radar`` stay out
+of scope (host random draws per pixel; an unstable sort decides the output)."""
 import ctypes as C
 import math
 
@@ -24,10 +32,124 @@ def center_crop_params(h, w, size):
     return int(round((h - th) / 2.)), int(round((w - tw) / 2.)), th, tw
 
 
-def stage_val_batch(image_u8, lidar_i16, radar_i16, crop_size=(450, 800), max_depth=float("inf")):
+# ------------------------------------------------------------------------------------------------ the radar_filtered sparsifier
+# The reference's __getitem__ runs filter_radar_points on every frame (:557-584, :638): it scatters the radar points into a dense
+# index_map, labels every radar point against the lidar ground truth (filter_radar_points_gt, dataset/radar_preprocessing.py:77-122)
+# and keeps valid_mask; transform_val / transform_train carry index_map through the depth maps' transform and, for
+# sparsifier="radar_filtered", zero the radar pixels whose index names a rejected point.  Here: filter_radar_points for a padded batch
+# of point sets (rd_radar_filter_points, rd_radar_index_map), then one launch behind rd_stage_frames / rd_stage_frames_train
+# (rd_stage_index_filter_val / _train).  Quirks kept: the distance count is over all three neighbours while the depth test looks at
+# the first ``count`` of them; the depth difference is signed; where the training rotation samples outside the frame index_map is 0
+# (scipy's cval), which names point 0.  Differences: index_map is int32 (the reference: an int64 array that its ToTensor hands out as
+# float32); a point whose truncated pixel lies
+# outside the frame is skipped (the reference wraps a negative index around and raises IndexError beyond the frame); one radar point
+# is labelled like any other count (the reference's np.squeeze breaks there).
+_FILTER_THRESHOLDS = np.array([np.log(4 / 14), np.log(14), np.log(16 / 5), np.log(5)], dtype=np.float64)      # sid_dist_thresh, sid_depth_thresh
+
+
+def _counts(n, B, what):
+    a = np.ascontiguousarray(np.asarray(n.cpu() if torch.is_tensor(n) else n).reshape(-1), dtype=np.int32)
+    if a.shape[0] != B:
+        raise ValueError("%s: %d counts for %d frames" % (what, a.shape[0], B))
+    return a
+
+
+class RadarFilter:
+    """What ``filter_radar_points`` keeps of a batch: index_map int32 [B,H0,W0] (-1 where no point falls), valid_mask bool [B,Rmax],
+    valid_labels uint8 [B,Rmax] (0 invalid, 1 valid, 2 unknown: no lidar point near), topk int32 [B,Rmax,3] (the neighbours by
+    distance, then index) on the GPU, and the host counts n_radar [B].  Rows at or beyond n_radar[b] hold 0 / False / -1."""
+
+    def __init__(self, index_map, valid_mask, valid_labels, topk, n_radar):
+        self.index_map, self.valid_mask, self.valid_labels, self.topk, self.n_radar = index_map, valid_mask, valid_labels, topk, n_radar
+
+    def __iter__(self):
+        return iter((self.index_map, self.valid_mask, self.valid_labels, self.topk, self.n_radar))
+
+    def with_mask(self, mask):
+        """The same frames with a caller's per-point mask [B,Rmax] (truthy = keep) in place of valid_mask: the reference's
+        ``radar_filtered2`` (``pred_labels``) is nothing else."""
+        assert torch.is_tensor(mask) and mask.is_cuda and tuple(mask.shape) == tuple(self.valid_mask.shape), "mask: [B,Rmax] on the GPU"
+        return RadarFilter(self.index_map, mask.to(torch.bool).contiguous(), self.valid_labels, self.topk, self.n_radar)
+
+
+def filter_radar_points(radar_points, radar_depth_points, lidar_points, lidar_depth_points, n_radar, n_lidar, frame_shape):
+    """The reference's per-frame ``filter_radar_points`` for a batch.  radar_points [B,Rmax,2] (x, y in pixels; a third column is
+    ignored), radar_depth_points [B,Rmax], lidar_points [B,Lmax,2 or 3], lidar_depth_points [B,Lmax]: padded GPU tensors, cast to
+    float64 if they are not; n_radar / n_lidar: the B host counts; frame_shape (H0, W0).  The padding is never read.  Returns a
+    ``RadarFilter``.  Everything is queued on the current stream; nothing synchronises with the host."""
+    pts = []
+    for t, what in ((radar_points, "radar_points"), (lidar_points, "lidar_points")):
+        assert torch.is_tensor(t) and t.is_cuda and t.dim() == 3 and t.shape[-1] in (2, 3), what + ": [B,N,2] or [B,N,3] on the GPU"
+        pts.append(t[..., :2].to(torch.float64).contiguous())
+    rxy, lxy = pts
+    B, Rmax, Lmax = rxy.shape[0], rxy.shape[1], lxy.shape[1]
+    assert lxy.shape[0] == B, "lidar_points: another batch size"
+    deps = []
+    for t, n, what in ((radar_depth_points, Rmax, "radar_depth_points"), (lidar_depth_points, Lmax, "lidar_depth_points")):
+        assert torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == (B, n), what + ": [B,N] on the GPU, padded like its points"
+        deps.append(t.to(torch.float64).contiguous())
+    rdep, ldep = deps
+    nr, nl = _counts(n_radar, B, "n_radar"), _counts(n_lidar, B, "n_lidar")
+    H0, W0 = (int(v) for v in frame_shape)
+    dev = rxy.device
+    labels = torch.empty(B, Rmax, dtype=torch.uint8, device=dev)
+    valid = torch.empty(B, Rmax, dtype=torch.uint8, device=dev)
+    topk = torch.empty(B, Rmax, 3, dtype=torch.int32, device=dev)
+    index_map = torch.empty(B, H0, W0, dtype=torch.int32, device=dev)
+    L, host = lib(), lambda a: C.c_void_p(a.ctypes.data)
+    check(L.rd_radar_filter_points(ptr(rxy), ptr(rdep), ptr(lxy), ptr(ldep), host(nr), host(nl), B, Rmax, Lmax, host(_FILTER_THRESHOLDS),
+                                   ptr(labels), ptr(valid), ptr(topk), current_stream()), "rd_radar_filter_points")
+    check(L.rd_radar_index_map(ptr(rxy), host(nr), B, Rmax, H0, W0, ptr(index_map), current_stream()), "rd_radar_index_map")
+    return RadarFilter(index_map, valid.view(torch.bool), labels, topk, nr)
+
+
+def _check_sparsifier(sparsifier, modality, radar_filter, extras):
+    """Whether the radar channel is to be filtered; raises what the reference raises for what it cannot feed either."""
+    if sparsifier in ("uniform", "lidar_radar"):
+        raise NotImplementedError("sparsifier %r is out of the staging's scope: uniform needs H*W host random draws per frame, lidar_radar "
+                                  "sorts pixel distances with an unstable argsort; staged are radar and radar_filtered" % sparsifier)
+    if sparsifier == "radar_filtered2":
+        raise NotImplementedError("[Error] The filtering method using point classifier is not supported in the released code.  Pass the "
+                                  "classifier's per-point mask as radar_filter.with_mask(mask) with sparsifier='radar_filtered'.")
+    if sparsifier not in ("radar", "radar_filtered"):
+        raise ValueError("[Error] Invalid sparsifier.")
+    if sparsifier == "radar_filtered":
+        if modality == "rgb":
+            raise ValueError("sparsifier 'radar_filtered' needs modality 'rgbd': modality 'rgb' has no radar channel to filter")
+        if radar_filter is None:
+            raise ValueError("sparsifier 'radar_filtered' needs radar_filter=filter_radar_points(...)")
+    if extras and radar_filter is None:
+        raise ValueError("extras=True needs radar_filter=filter_radar_points(...): index_map comes from it")
+    if radar_filter is not None and not isinstance(radar_filter, RadarFilter):
+        raise ValueError("radar_filter: a RadarFilter (filter_radar_points)")
+    return sparsifier == "radar_filtered"
+
+
+def _filter_geometry(radar_filter, B, H0, W0, dev):
+    f = radar_filter
+    assert tuple(f.index_map.shape) == (B, H0, W0) and f.index_map.dtype == torch.int32 and f.index_map.device == dev, \
+        "radar_filter was made for another batch or frame size"
+    assert f.valid_mask.dtype == torch.bool and f.valid_mask.dim() == 2 and f.valid_mask.shape[0] == B and len(f.n_radar) == B
+    return f.index_map.contiguous(), f.valid_mask.contiguous(), f.valid_mask.shape[1]
+
+
+def _with_extras(inputs, labels, index_map, extras):
+    """(inputs, labels), plus the reference's extra keys when asked for (radar_depth_filtered is a view of inputs' radar channel)."""
+    if not extras:
+        return inputs, labels
+    return inputs, labels, {"index_map": index_map, "radar_depth_filtered": inputs[:, 3:4] if inputs.shape[1] == 4 else None}
+
+
+def stage_val_batch(image_u8, lidar_i16, radar_i16, crop_size=(450, 800), max_depth=float("inf"), sparsifier="radar", radar_filter=None,
+                    extras=False):
     """image_u8 [B,H0,W0,3] uint8, lidar_i16 / radar_i16 [B,H0,W0] int16 (metres * 256), all on the GPU.
     Returns (inputs [B,4,th,tw], labels [B,1,th,tw]) fp32, like ``output_dict["inputs"], output_dict["labels"]`` stacked over
-    the batch.  max_depth < 0 means no clamp, as in main.py:71."""
+    the batch.  max_depth < 0 means no clamp, as in main.py:71.
+    sparsifier "radar_filtered" needs ``radar_filter`` (``filter_radar_points`` of the same frames): channel 3 of inputs is then the
+    filtered, clamped radar depth.  extras=True (with a radar_filter, whatever the sparsifier: the reference emits index_map for all)
+    adds a third value {"index_map": int32 [B,1,th,tw] (the reference: int64, float32 after its ToTensor), "radar_depth_filtered": view of
+    inputs[:, 3:4]}."""
+    apply = _check_sparsifier(sparsifier, "rgbd", radar_filter, extras)
     assert image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 4 and image_u8.shape[-1] == 3, "image: uint8 [B,H,W,3] on the GPU"
     B, H0, W0, _ = image_u8.shape
     for t in (lidar_i16, radar_i16):
@@ -39,7 +161,13 @@ def stage_val_batch(image_u8, lidar_i16, radar_i16, crop_size=(450, 800), max_de
     labels = torch.empty(B, 1, th, tw, dtype=torch.float32, device=image_u8.device)
     check(lib().rd_stage_frames(ptr(image_u8), ptr(lidar_i16), ptr(radar_i16), B, H0, W0, i0, j0, th, tw, C.c_float(md),
                                 ptr(inputs), ptr(labels), current_stream()), "rd_stage_frames")
-    return inputs, labels
+    index_map = None
+    if apply or extras:
+        src, valid, Rmax = _filter_geometry(radar_filter, B, H0, W0, image_u8.device)
+        index_map = torch.empty(B, 1, th, tw, dtype=torch.int32, device=image_u8.device)
+        check(lib().rd_stage_index_filter_val(ptr(src), ptr(valid), C.c_void_p(radar_filter.n_radar.ctypes.data), B, Rmax, H0, W0, i0, j0, th, tw,
+                                              int(apply), ptr(inputs), ptr(index_map), current_stream()), "rd_stage_index_filter_val")
+    return _with_extras(inputs, labels, index_map, extras)
 
 
 # ------------------------------------------------------------------------------------------------ training input (transform_train)
@@ -213,13 +341,18 @@ def prepare_train_params(params, h0, w0, crop_size=(450, 800), device="cuda"):
     return PreparedTrainParams(recs, host.to(device, non_blocking=True), off, (h0, w0), tuple(crop_size))
 
 
-def stage_train_batch(image_u8, lidar_i16, radar_i16, params, crop_size=(450, 800), max_depth=float("inf"), modality="rgbd"):
+def stage_train_batch(image_u8, lidar_i16, radar_i16, params, crop_size=(450, 800), max_depth=float("inf"), modality="rgbd", sparsifier="radar",
+                      radar_filter=None, extras=False):
     """The reference's ``transform_train`` for a whole batch on the GPU, bit-identical to it for the same draws.
     image_u8 [B,H0,W0,3] uint8, lidar_i16 / radar_i16 [B,H0,W0] int16 (metres * 256) on the GPU as for ``stage_val_batch``; ``params``
     from ``draw_train_params(B, crop_size, ...)``, or what ``prepare_train_params`` made of them ahead of time.  Returns
     (inputs [B,4,ch,cw], labels [B,1,ch,cw]) fp32; with modality "rgb" the radar argument may be None and inputs is [B,3,ch,cw].  max_depth < 0 means no clamp, as in main.py:71.  Everything is queued on
-    the current stream; nothing synchronises with the host."""
+    the current stream; nothing synchronises with the host.
+    sparsifier / radar_filter / extras as for ``stage_val_batch``: with "radar_filtered" (modality rgbd only) channel 3 is the filtered,
+    clamped radar depth; index_map goes through the depth maps' rotation, NEAREST resize, crop and flip, with 0 (the rotation's cval, not
+    -1) where the rotation samples outside the frame."""
     assert modality in ("rgbd", "rgb"), "modality: rgbd or rgb"
+    apply = _check_sparsifier(sparsifier, modality, radar_filter, extras)
     assert image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 4 and image_u8.shape[-1] == 3, "image: uint8 [B,H,W,3] on the GPU"
     B, H0, W0, _ = image_u8.shape
     depth = (lidar_i16,) if modality == "rgb" and radar_i16 is None else (lidar_i16, radar_i16)
@@ -242,4 +375,12 @@ def stage_train_batch(image_u8, lidar_i16, radar_i16, params, crop_size=(450, 80
     check(L.rd_stage_frames_train(ptr(image_u8), ptr(lidar_i16), ptr(radar_i16), B, H0, W0, ch, cw, C.c_void_p(prep.records.ctypes.data),
                                   *[C.c_void_p(base + 4 * o) for o in prep.offsets], ptr(work), C.c_float(md), 1 if modality == "rgb" else 0,
                                   ptr(inputs), ptr(labels), current_stream()), "rd_stage_frames_train")
-    return inputs, labels
+    index_map = None
+    if apply or extras:
+        src, valid, Rmax = _filter_geometry(radar_filter, B, H0, W0, dev)
+        index_map = torch.empty(B, 1, ch, cw, dtype=torch.int32, device=dev)
+        check(L.rd_stage_index_filter_train(ptr(src), ptr(valid), C.c_void_p(radar_filter.n_radar.ctypes.data), B, Rmax, H0, W0, ch, cw,
+                                            C.c_void_p(prep.records.ctypes.data), C.c_void_p(base + 4 * prep.offsets[0]),
+                                            C.c_void_p(base + 4 * prep.offsets[1]), int(apply), ptr(inputs) if apply else None, ptr(index_map),
+                                            current_stream()), "rd_stage_index_filter_train")
+    return _with_extras(inputs, labels, index_map, extras)
