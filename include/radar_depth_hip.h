@@ -624,6 +624,55 @@ int rd_stage_index_filter_train(const int32_t* index_map, const uint8_t* valid, 
                                 int32_t H0, int32_t W0, int32_t ch, int32_t cw, const RdStageTrainFrame* frames, const int32_t* near_y,
                                 const int32_t* near_x, int32_t apply_filter, float* inputs, int32_t* index_map_out, void* stream);
 
+/* The lidar sparsifiers (csrc/lidar_sparsify.hip): the reference's LidarRadarSampling and UniformSampling (dataset/dense_to_sparse.py)
+ * behind get_sparse_depth (dataset/nuscenes_dataset_torch_new.py:200-216), on the staged depth planes of a whole batch.  Planes are
+ * fp32 device arrays of B frames; each frame is H*W contiguous pixels and frame b starts `stride` ELEMENTS after frame b-1 (stride >=
+ * H*W: channel 3 of a [B,4,H,W] tensor has stride 4*H*W).  `workspace`: rd_lidar_sparsify_workspace_bytes(B, H, W) bytes on the
+ * device, 16-byte aligned, the same size for both; no state survives the call.  One memset and two launches per call whatever B is,
+ * on `stream`; no allocation, no host synchronisation, the per-frame counts never reach the host.  The only atomics are integer adds
+ * whose order cannot change the result: the output is bit-reproducible from run to run.
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_ESPARSE_NULL      a null pointer (draws and mask of rd_uniform_sparsify may be null)
+ *   RD_ESPARSE_RANGE     B outside 1..65535, H or W outside 1..46340 (a squared pixel distance has to fit 32 bits)
+ *   RD_ESPARSE_PIXELS    H*W >= 2^30
+ *   RD_ESPARSE_STRIDE    a batch stride smaller than H*W
+ *   RD_ESPARSE_SAMPLES   num_samples < 0
+ *   RD_ESPARSE_MAXDEPTH  max_depth is NaN
+ *   RD_ESPARSE_OVERLAP   out shares memory with an input plane without being exactly that plane (same pointer, same stride); the
+ *                        lidar plane of rd_lidar_radar_sparsify may not be out at all.  Planes with different batch strides are
+ *                        judged by their whole extents.
+ * rd_lidar_sparsify_workspace_bytes returns RD_EINVAL for a geometry the calls reject. */
+#define RD_ESPARSE_NULL (-20)
+#define RD_ESPARSE_RANGE (-21)
+#define RD_ESPARSE_PIXELS (-22)
+#define RD_ESPARSE_STRIDE (-23)
+#define RD_ESPARSE_SAMPLES (-24)
+#define RD_ESPARSE_MAXDEPTH (-25)
+#define RD_ESPARSE_OVERLAP (-26)
+int64_t rd_lidar_sparsify_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* lidar_radar.  Radar pixels are radar > 0, lidar pixels lidar > 0 (no max_depth enters).  Per radar pixel the two lidar pixels that
+ * come first by (dy*dy + dx*dx as an integer, row-major linear index): equal distances go to the lower index (the reference's
+ * argsort is unstable there; the two agree wherever a radar pixel's second and third nearest lidar pixels are not equidistant).
+ * out = lidar at the union of the chosen pixels, 0 elsewhere; a frame without a radar pixel or without a lidar pixel comes out all
+ * zero, a frame with one lidar pixel keeps that one.  `out` may be the radar plane itself (the radar pixels are collected before the
+ * plane is cleared); it must not overlap `lidar`. */
+int rd_lidar_radar_sparsify(const float* lidar, int64_t lidar_stride, const float* radar, int64_t radar_stride, int32_t B, int32_t H,
+                            int32_t W, void* workspace, float* out, int64_t out_stride, void* stream);
+/* uniform.  keep = depth > 0 && depth <= (float)max_depth (torch compares an fp32 tensor with a Python float in fp32; +inf: no
+ * clamp); n_keep = count(keep) per frame; prob = (double)num_samples / (double)n_keep (IEEE float64 division);
+ * out = depth where keep && U < prob (strict), 0 elsewhere; n_keep == 0 gives an all-zero frame without a division.  mask (may be
+ * NULL): uint8 [B,H*W] contiguous, 1 where a pixel was kept.  out may be the depth plane itself.
+ * U: `draws`, float64 [B,H*W] contiguous -- the reference's np.random.uniform(0, 1, depth.shape) of every frame, which makes the
+ * result bit-identical to the reference's -- or, when draws is NULL, the device generator, which is part of the interface:
+ *   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85)
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (pixel's row-major linear index, frame & 0xffffffff, frame >> 32, 0),  frame = frame0 + b
+ *   U       = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53  from the output words x0, x1 (numpy's 53-bit recipe), so 0 <= U < 1. */
+int rd_uniform_sparsify(const float* depth, int64_t depth_stride, int32_t B, int32_t H, int32_t W, int64_t num_samples, double max_depth,
+                        const double* draws, uint64_t seed, uint64_t frame0, void* workspace, float* out, int64_t out_stride,
+                        uint8_t* mask, void* stream);
+
 /* NCHW [N,C,H,W] (channel c0..c0+C of Ctot) <-> NHWC helpers for module-level tests */
 int rd_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

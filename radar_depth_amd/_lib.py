@@ -14,6 +14,9 @@ RD_MAX_PHASES = 4
 ACT_NONE, ACT_RELU, ACT_LEAKY02 = 0, 1, 2
 # argument-check codes of the radar_filtered entry points (include/radar_depth_hip.h)
 RD_ERADAR_NULL, RD_ERADAR_RANGE, RD_ERADAR_NRADAR, RD_ERADAR_NLIDAR, RD_ERADAR_FEWLIDAR, RD_ERADAR_CROP = -10, -11, -12, -13, -14, -15
+# ... and of the lidar sparsifiers
+RD_ESPARSE_NULL, RD_ESPARSE_RANGE, RD_ESPARSE_PIXELS, RD_ESPARSE_STRIDE, RD_ESPARSE_SAMPLES, RD_ESPARSE_MAXDEPTH = -20, -21, -22, -23, -24, -25
+RD_ESPARSE_OVERLAP = -26
 
 
 class RdPhase(C.Structure):
@@ -63,7 +66,8 @@ def lib():
         _lib.rd_last_error.restype = C.c_char_p
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
-                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats"):
+                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats",
+                     "rd_lidar_sparsify_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
         # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
@@ -77,7 +81,12 @@ def lib():
                            ("rd_radar_filter_points", [vp] * 6 + [C.c_int32] * 3 + [vp] * 5),
                            ("rd_radar_index_map", [vp, vp] + [C.c_int32] * 4 + [vp, vp]),
                            ("rd_stage_index_filter_val", [vp] * 3 + [C.c_int32] * 9 + [vp] * 3),
-                           ("rd_stage_index_filter_train", [vp] * 3 + [C.c_int32] * 6 + [vp] * 3 + [C.c_int32] + [vp] * 3)):
+                           ("rd_stage_index_filter_train", [vp] * 3 + [C.c_int32] * 6 + [vp] * 3 + [C.c_int32] + [vp] * 3),
+                           # the lidar sparsifiers (csrc/lidar_sparsify.hip)
+                           ("rd_lidar_sparsify_workspace_bytes", [C.c_int32] * 3),
+                           ("rd_lidar_radar_sparsify", [vp, C.c_int64, vp, C.c_int64] + [C.c_int32] * 3 + [vp, vp, C.c_int64, vp]),
+                           ("rd_uniform_sparsify", [vp, C.c_int64] + [C.c_int32] * 3 + [C.c_int64, C.c_double, vp, C.c_uint64, C.c_uint64, vp, vp,
+                                                                                      C.c_int64, vp, vp])):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = args
     return _lib

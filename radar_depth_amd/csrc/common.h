@@ -46,6 +46,15 @@ void set_error(const char* fmt, ...);
         }                                   \
     } while (0)
 
+// the same with a code of the entry point's own (RD_ERADAR_*, RD_ESPARSE_*)
+#define RD_CHECK_CODE(cond, code, ...)      \
+    do {                                    \
+        if (!(cond)) {                      \
+            rd::set_error(__VA_ARGS__);     \
+            return code;                    \
+        }                                   \
+    } while (0)
+
 #define RD_CHECK_LAUNCH(what)                                                     \
     do {                                                                          \
         hipError_t e__ = hipGetLastError();                                       \

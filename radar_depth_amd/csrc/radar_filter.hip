@@ -26,14 +26,6 @@
 
 namespace rd {
 
-#define RD_CHECK_CODE(cond, code, ...)      \
-    do {                                    \
-        if (!(cond)) {                      \
-            rd::set_error(__VA_ARGS__);     \
-            return code;                    \
-        }                                   \
-    } while (0)
-
 struct RadarCounts { int32_t nr[kChunk], nl[kChunk]; };
 
 constexpr int kNoIndex = INT_MAX;       // the index of an empty top-three slot: sorts after every lidar point at the same distance

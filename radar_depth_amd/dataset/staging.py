@@ -16,7 +16,8 @@ lidar points -- per-point labels, ``valid_mask``, the dense ``index_map`` -- and
 (``sparsifier="radar_filtered", radar_filter=..., extras=...``): ``index_map`` follows the depth maps through the transform and the radar
 returns the filter rejected are zeroed, equal to the reference's output for the same frames, points and draws
 (``rd_radar_filter_points``, ``rd_radar_index_map``, ``rd_stage_index_filter_val`` / ``_train``).  ``uniform`` and ``lidar_radar`` stay out
-of scope (host random draws per pixel; an unstable sort decides the output)."""
+of the staging calls' scope: they work on the staged planes and live in dense_to_sparse.py (``uniform_sparse_depth``,
+``lidar_radar_sparse_depth``)."""
 import ctypes as C
 import math
 
@@ -106,8 +107,9 @@ def filter_radar_points(radar_points, radar_depth_points, lidar_points, lidar_de
 def _check_sparsifier(sparsifier, modality, radar_filter, extras):
     """Whether the radar channel is to be filtered; raises what the reference raises for what it cannot feed either."""
     if sparsifier in ("uniform", "lidar_radar"):
-        raise NotImplementedError("sparsifier %r is out of the staging's scope: uniform needs H*W host random draws per frame, lidar_radar "
-                                  "sorts pixel distances with an unstable argsort; staged are radar and radar_filtered" % sparsifier)
+        raise NotImplementedError("sparsifier %r is out of the staging's scope (staged are radar and radar_filtered): stage with "
+                                  "sparsifier='radar' and max_depth=inf, then call radar_depth_amd.dataset.uniform_sparse_depth / "
+                                  "lidar_radar_sparse_depth with out=inputs[:, 3:4]" % sparsifier)
     if sparsifier == "radar_filtered2":
         raise NotImplementedError("[Error] The filtering method using point classifier is not supported in the released code.  Pass the "
                                   "classifier's per-point mask as radar_filter.with_mask(mask) with sparsifier='radar_filtered'.")
