@@ -19,6 +19,7 @@ ReLU / LeakyReLU, residual joins and max-pool follow models.py:96-112,203-208,63
 import contextlib
 import ctypes as C
 import os
+import types
 
 import torch
 
@@ -349,233 +350,314 @@ class LateFusionPlan:
             check(int(n), "rd_gconv_workspace_floats(%s)" % name)
         return self.buf(int(n)) if n > 0 else None
 
-    def conv_fwd(self, name, x, weights, k, stride, pad, out=None, kind="conv", lst=None):
-        """weights: list of (param, column offset), OIHW params except for kind "deconv" (CONV_KINDS).  Returns (raw Act, ctx)."""
-        assert kind in CONV_KINDS
-        lst = self.fwd if lst is None else lst
-        N, H, W = x.N, x.H, x.W
-        deconv = kind == "deconv"
-        cout = sum(w.shape[1 if deconv else 0] for w, _ in weights)
-        cin = x.C
-        if deconv:
-            assert len(weights) == 1 and weights[0][1] == 0 and stride == 2 and pad == cd.deconv_pad(k)
-            d = cd.deconv_fwd(N, H, W, cin, cout, k, ldi=x.ld)
-        elif kind == "upproj":
-            d = cd.upproj_fwd(N, H, W, cin, cout, ldi=x.ld)
-        else:
-            d = cd.conv_fwd(N, H, W, cin, cout, k, stride, pad, ldi=x.ld)
-        if out is None:
-            out = self.act(N, d.Ho, d.Wo, cout)
-        d.ldo = out.ld
-        S = k * k
-        wdt = torch.bfloat16 if self.bf16 else torch.float32
-        quad = 2 if self.bf16 else 1
-        # split plans: each of the two operands (forward, input gradient) is packed as three bf16 piece planes when the library has a
-        # split plan for that descriptor, and stays the fp32 operand of rd_gconv otherwise
-        sp_f = sp_d = pre_f = pre_d = c16 = False
+    # ---- descriptors, the family decision, one launch emitter per family
+    def _desc(self, kind, grad, x, cout, k, stride, pad, **ld):
+        """Forward (grad=False; ldi=) or input-gradient (grad=True; ld_dy=, ld_dx=) descriptor of a CONV_KINDS convolution on the input
+        Act x -> (descriptor, whether a strided input gradient leaves the pixels between its strides unwritten)."""
+        g = (x.N, x.H, x.W, x.C, cout)
+        if kind == "deconv":
+            assert stride == 2 and pad == cd.deconv_pad(k)
+            return (cd.deconv_dgrad if grad else cd.deconv_fwd)(*g, k, **ld), False
+        if kind == "upproj":
+            return (cd.upproj_dgrad if grad else cd.upproj_fwd)(*g, **ld), False
+        return cd.conv_dgrad(*g, k, stride, pad, **ld) if grad else (cd.conv_fwd(*g, k, stride, pad, **ld), False)
+
+    # families (self.meta names) whose weight operand is three bf16 piece planes [3][taps][rows][cols]
+    PIECE_OPERAND = ("gconv_split_pre", "gconv_split", "gemm_taps_split")
+
+    def _conv_families(self, kind, x, out, d, k, stride, pad, weights):
+        """Kernel families (self.meta names) of a training convolution's forward and input-gradient launches.  Both are decided here, in
+        conv_fwd, because the family determines how the weight operand is packed; the input gradient's is decided on a provisional
+        descriptor (default strides) and confirmed against the final one in conv_bwd (_confirm_dgrad)."""
+        L, cin, cout = self.L, x.C, out.C
+        base = "gconv_bf16" if self.bf16 else "gconv"
+        if not self.split:
+            return base, base
+        dd0 = self._desc(kind, True, x, cout, k, stride, pad)[0]
+
+        def direct(dsc, pre_ok):
+            # split plans: an operand is packed as three bf16 piece planes when the library has a split plan for that descriptor, and stays the
+            # fp32 operand of rd_gconv otherwise.  The pre-split form (operand split by its producer, gconv_sp2_kernel) where the library
+            # expects it to win even after the producer's extra piece pass -- incl. 32-channel layers rd_gconv_split does not serve
+            sp = L.rd_gconv_split_supported(C.byref(dsc)) == 1
+            pre = pre_ok and L.rd_gconv_split_pre_supported(C.byref(dsc)) == 1 and L.rd_gconv_split_pre_preferred(C.byref(dsc)) == 1
+            return "gconv_split_pre" if pre else "gconv_split" if sp else None
+        # split plans: the 16 -> 16 channel 3x3 layers (depth encoder layer1, dec4 conv2) with three-piece operands too
+        # (csrc/conv16_split.hip: conv16.hip's contract, tiling and fp32 weight operand); the input gradient's on the final descriptor
+        fam_f = direct(d, self._pre_ok(x)) or ("conv16_split" if self._c16_split(d) else base)
+        # (the input gradient's operand is a [N,Ho,Wo,cout] tensor the BatchNorm backward produces: same alignment rule)
+        fam_d = direct(dd0, self.pre and cout % 16 == 0) or base
         # Winograd F(2x2,3x3) on the split pipeline (csrc/wino_split.hip) for the 3x3 / stride-1 layers where the kernel-level gate measured
         # it ahead of the direct split kernels (rd_wino_preferred: 512-channel layers, small maps with <= 128 channels); forward and input
         # gradient decided separately (the input gradient is the same kernel on the flipped operand, channels swapped)
-        wino_f = wino_d = False
-        if self.split and self.train and kind == "conv" and k == 3 and stride == 1 and pad == 1 and len(weights) == 1 and weights[0][1] == 0:
-            wino_f = self.L.rd_wino_preferred(H, W, cin, cout, x.ld, out.ld if out is not None else cout) == 1
-            wino_d = self.L.rd_wino_preferred(H, W, cout, cin, cout, cin) == 1
-        if self.split:
-            sp_f = self.L.rd_gconv_split_supported(C.byref(d)) == 1
-            dd0 = (cd.deconv_dgrad(N, H, W, cin, cout, k) if deconv else cd.upproj_dgrad(N, H, W, cin, cout) if kind == "upproj"
-                   else cd.conv_dgrad(N, H, W, cin, cout, k, stride, pad)[0])
-            sp_d = self.L.rd_gconv_split_supported(C.byref(dd0)) == 1
-            # the pre-split form (operand split by its producer, gconv_sp2_kernel) where the library expects it to win even after the
-            # producer's extra piece pass -- incl. 32-channel layers rd_gconv_split does not serve
-            pre_f = (self._pre_ok(x) and self.L.rd_gconv_split_pre_supported(C.byref(d)) == 1
-                     and self.L.rd_gconv_split_pre_preferred(C.byref(d)) == 1)
-            sp_f = sp_f or pre_f
-            # (the input gradient's operand is a [N,Ho,Wo,cout] tensor the BatchNorm backward produces: same alignment rule)
-            pre_d = (self.pre and cout % 16 == 0 and self.L.rd_gconv_split_pre_supported(C.byref(dd0)) == 1
-                     and self.L.rd_gconv_split_pre_preferred(C.byref(dd0)) == 1)
-            sp_d = sp_d or pre_d
-            if wino_f:
-                sp_f = pre_f = False
-            if wino_d:
-                sp_d = pre_d = False
+        if self.train and kind == "conv" and k == 3 and stride == 1 and pad == 1 and len(weights) == 1 and weights[0][1] == 0:
+            if L.rd_wino_preferred(x.H, x.W, cin, cout, x.ld, out.ld) == 1:
+                fam_f = "wino"
+            if L.rd_wino_preferred(x.H, x.W, cout, cin, cout, cin) == 1:
+                fam_d = "wino"
         # the few-tap channel-grouped kernel (csrc/gemm_taps_split.hip) where its gate measured it ahead: deconv2's input gradient
-        taps_d = self.split and deconv and self.L.rd_gemm_taps_split_preferred(C.byref(dd0)) == 1
-        if taps_d:
-            sp_d, pre_d = True, False
-        self.L.rd_wino_packed_bytes.restype = C.c_int64
-        uf = ud = None
-        if wino_f:
-            wp = None
-            uf = self.buf(int(self.L.rd_wino_packed_bytes(cout, cin, 0)) // 2, dtype=torch.bfloat16)
-            self.wino_jobs.append((weights[0][0], uf, cout, cin, 0))
-        else:
-            wp = self.buf(3, S, cin, cout, dtype=torch.bfloat16) if sp_f else self.buf(S, cin, cout, dtype=wdt)
-        if wino_d:
-            wd = None
-            ud = self.buf(int(self.L.rd_wino_packed_bytes(cout, cin, 1)) // 2, dtype=torch.bfloat16)
-            self.wino_jobs.append((weights[0][0], ud, cout, cin, 1))
-        else:
-            wd = self.buf(3, S, cout, cin, dtype=torch.bfloat16) if sp_d else self.buf(S, cout, cin, dtype=wdt)
-        for w, off in weights:
-            o, i, kh, kw = w.shape
-            if deconv:
-                # the [Cin, Cout, k, k] weight read as the adjoint conv's OIHW weight (O = cin, I = cout): the forward is that conv's input
-                # gradient (transposed operand [slab][cin][cout]), the input gradient its forward (plain operand [slab][cout][cin])
-                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, 0, cin, 1, None, 3 if sp_f else quad))
-                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, 0, i, 0, None, 3 if sp_d else quad))
-                continue
-            if not wino_f:
-                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, off, i, 0, None, 3 if sp_f else quad))
-            if not wino_d:
-                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, off, cout, 1, None, 3 if sp_d else quad))
-        if not sp_f and not wino_f:
-            self._tune(d)
-        if wino_f:
-            tiles = self.L.rd_wino_stat_tiles(N, H, W)
-        elif self.bf16 and not sp_f:
-            tiles = self.L.rd_gconv_bf16_stat_tiles_t(self.dt, C.byref(d))      # (bf16 storage: the persistent kernel's own tiling)
-        else:
-            tiles = (self.L.rd_gconv_split_pre_stat_tiles if pre_f else self.L.rd_gconv_split_stat_tiles if sp_f else
-                     self.L.rd_gconv_stat_tiles_ws)(C.byref(d))
-        if tiles < 0:
-            check(tiles, "rd_gconv_stat_tiles(%s)" % name)
-        stat = self.buf(tiles, 2, cout) if self.train else None
-        self.keep.append(d)
-        if wino_f:
-            if self.L.rd_wino_supported(H, W, cin, cout, x.ld, out.ld) != 1:
-                raise RuntimeError("%s: planned as a Winograd layer, but the library does not serve %dx%d %d->%d with strides %d / %d" % (name, H, W, cin, cout, x.ld, out.ld))
-            self.op(lst, name, self.L.rd_wino_conv3x3, x.ptr, N, H, W, cin, x.ld, _p(uf), out.ptr, cout, out.ld, C.c_void_p(0), 0, _p(stat), self.stream)
-        elif pre_f:
-            xp, xplane = self.pc_in(x, lst)
-            self.op(lst, name, self.L.rd_gconv_split_pre, C.byref(d), xp, xplane, _p(wp), C.c_int64(S * cin * cout), out.ptr, C.c_void_p(0), 0, 0,
-                    C.c_void_p(0), 0, _p(stat), self.stream)
-        elif sp_f:
-            self.op(lst, name, self.L.rd_gconv_split, C.byref(d), x.ptr, _p(wp), C.c_int64(S * cin * cout), out.ptr, C.c_void_p(0), 0, 0,
-                    C.c_void_p(0), 0, _p(stat), self.stream)
-        elif self.bf16:
-            self.op(lst, name, self.L.rd_gconv_bf16_t, self.dt, C.byref(d), x.ptr, _p(wp), out.ptr, C.c_void_p(0), 0, 0, C.c_void_p(0), 0,
-                    _p(stat), self.stream)
-        elif self._c16_split(d):
-            # split plans: the 16 -> 16 channel 3x3 layers (depth encoder layer1, dec4 conv2) with three-piece operands too
-            # (csrc/conv16_split.hip: conv16.hip's contract, tiling and fp32 weight operand)
-            c16 = True
-            self.op(lst, name, self.L.rd_conv16_split, C.byref(d), x.ptr, _p(wp), out.ptr, C.c_void_p(0), 0, _p(stat), self.stream)
-        else:
-            ws = self._gconv_ws(d, name)
-            self.op(lst, name, self.L.rd_gconv_ws, C.byref(d), x.ptr, _p(wp), out.ptr, C.c_void_p(0), 0, _p(stat), _p(ws), self.stream)
-        self.taps[name] = out
-        self.meta[name] = ("wino" if wino_f else "gconv_split_pre" if pre_f else "gconv_split" if sp_f else "gconv_bf16" if self.bf16 else "conv16_split" if c16 else "gconv", d)
-        ctx = dict(name=name, d=d, x=x, out=out, weights=weights, wd=wd, k=k, stride=stride, pad=pad, kind=kind,
-                   stat=stat, tiles=tiles, cin=cin, cout=cout, split_dgrad=sp_d, pre_dgrad=self.split and pre_d, wino_dgrad=wino_d, ud=ud,
-                   taps_dgrad=self.split and taps_d)
-        return out, ctx
+        if kind == "deconv" and L.rd_gemm_taps_split_preferred(C.byref(dd0)) == 1:
+            fam_d = "gemm_taps_split"
+        return fam_f, fam_d
 
     def _c16_split(self, d):
         return (self.split and not self.bf16 and os.environ.get("RD_CONV16_SPLIT", "1") == "1"
                 and self.L.rd_conv16_split_supported(C.byref(d)) == 1)
 
+    def _confirm_dgrad(self, ctx, dd, dout, dx, have_planes, zero_fill):
+        """The input-gradient family conv_fwd planned (ctx["dgrad"]), confirmed against the final descriptor dd."""
+        fam, name, x = ctx["dgrad"], ctx["name"], ctx["x"]
+        if fam == "wino":
+            # the input gradient of a Winograd layer: the same kernel on the flipped operand (channels swapped, taps rotated by 180 degrees)
+            if zero_fill or self.L.rd_wino_supported(x.H, x.W, dout.C, x.C, dout.ld, dx.ld) != 1:
+                raise RuntimeError("%s: planned as a Winograd input gradient, but the library does not serve %dx%d %d->%d with strides %d / %d"
+                                   % (name, x.H, x.W, dout.C, x.C, dout.ld, dx.ld))
+        elif fam == "gemm_taps_split":
+            if self.L.rd_gemm_taps_split_supported(C.byref(dd)) != 1:
+                raise RuntimeError("%s: planned on rd_gemm_taps_split, but the library does not serve the final input-gradient descriptor" % name)
+        elif fam in self.PIECE_OPERAND:
+            pre = fam == "gconv_split_pre" and have_planes and self.L.rd_gconv_split_pre_supported(C.byref(dd)) == 1
+            if not pre and self.L.rd_gconv_split_supported(C.byref(dd)) != 1:
+                raise RuntimeError("%s: the input-gradient operand was packed as three bf16 pieces, but the library has neither a split plan for "
+                                   "the final descriptor nor piece planes for its output-gradient tensor" % name)
+            fam = "gconv_split_pre" if pre else "gconv_split"
+        elif fam == "gconv":
+            if self._c16_split(dd):
+                return "conv16_split"
+            self._tune(dd)      # (plans the descriptor: table pin / tuner first -- the fusion test, tiles and workspace depend on the plan)
+        return fam
+
+    def _wgrad_family(self, name, dwd, x, dout, deconv):
+        """Kernel family (self.meta name) of a convolution's weight-gradient launch."""
+        wenv = os.environ.get
+        if self.storage == "bf16":
+            # bf16 tensors: only the bf16 weight-gradient kernel reads them (the 16-channel layers included: a half-empty
+            # 32-wide tile, but half the bytes and no conversion in its staging waves)
+            if self.L.rd_wgrad_bf16_supported(C.byref(dwd)) != 1:
+                raise NotImplementedError("bf16 storage: no bf16 weight-gradient decomposition for %s" % name)
+            return "wgrad_bf16"
+        # bf16 plans: the weight gradients run on the bf16 matrix cores as well (3x3 / 1x1 at both strides, UpProj 5x5); what the
+        # bf16 kernel cannot decompose keeps the fp32 kernel
+        # (32-wide MFMA tiles: the 16-channel layers are faster on the fp32 kernel -- 42 vs 55 us for the depth encoder's layer1)
+        if (self.bf16 and wenv("RD_WGRAD_BF16", "1") == "1" and min(x.C, dout.C) >= int(wenv("RD_WGRAD_BF16_MINC", "32"))
+                and self.L.rd_wgrad_bf16_supported(C.byref(dwd)) == 1):
+            return "wgrad_bf16"
+        # split plans: the 3x3 / stride-1 weight gradients with >= 64 channels run on the bf16 matrix cores as well (csrc/wgrad_split.hip:
+        # both operands split into three bf16 pieces while they are staged); same slabs, same deterministic reduction
+        if not (self.split and not self.batch_reduces and wenv("RD_WGRAD_SPLIT", "1") == "1" and self.L.rd_wgrad_split_supported(C.byref(dwd)) == 1):
+            return "wgrad"
+        # (the weight gradient keeps splitting while it stages: its pre-split form measured 0.8-0.9x, profiles/r04_bench_wgrad_split.txt;
+        #  RD_WGRAD_PRE=1 opts in)
+        pre = (not deconv and wenv("RD_WGRAD_PRE", "0") == "1" and self._pre_ok(x) and self._pre_ok(dout)
+               and self.L.rd_wgrad_split_pre_supported(C.byref(dwd)) == 1)
+        return "wgrad_split_pre" if pre else "wgrad_split"
+
+    def _stat_tiles(self, fam, d, x):
+        """Rows of the per-tile partial sums a launch of family fam writes (BatchNorm statistics, or the sums of a *_bnbwd epilogue)."""
+        if fam == "wino":
+            return self.L.rd_wino_stat_tiles(x.N, x.H, x.W)
+        if fam == "gconv_bf16":
+            return self.L.rd_gconv_bf16_stat_tiles_t(self.dt, C.byref(d))      # (bf16 storage: the persistent kernel's own tiling)
+        return {"gconv_split_pre": self.L.rd_gconv_split_pre_stat_tiles, "gconv_split": self.L.rd_gconv_split_stat_tiles}.get(
+            fam, self.L.rd_gconv_stat_tiles_ws)(C.byref(d))
+
+    # shared argument tails
+    @staticmethod
+    def _addend(a):
+        """(pointer, channel stride) of an optional Act argument -- a residual addend, a second operand."""
+        return (a.ptr, a.ld) if a is not None else (C.c_void_p(0), 0)
+
+    @staticmethod
+    def _bnb_tail(bnb, red):
+        xb, co = bnb["x"], bnb["co"]
+        return xb.ptr, xb.ld, _p(co["mean"]), _p(co["scale"]), _p(co["shift"]), bnb["act"], _p(red)
+
+    def _emit_wino(self, q):
+        geom = (q.x.ptr, q.x.N, q.x.H, q.x.W, q.x.C, q.x.ld, _p(q.w), q.out.ptr, q.out.C, q.out.ld)
+        if q.bnb:
+            # the BatchNorm behind this convolution's forward input takes its backward sums from this launch's epilogue (one
+            # rd_bn_bwd_reduce_x_t pass over dx and x less per conv -> BN -> ReLU -> conv chain; VERDICT r5 item 2b, second half)
+            self.op(q.lst, q.name, self.L.rd_wino_conv3x3_bnbwd, *geom, *q.bnb, self.stream)
+        else:
+            self.op(q.lst, q.name, self.L.rd_wino_conv3x3, *geom, *self._addend(q.addend), _p(q.stat), self.stream)
+
+    def _emit_pieces(self, q):
+        """rd_gconv_split / rd_gconv_split_pre (input as piece planes) / rd_gemm_taps_split: three-piece weight operand."""
+        pre = q.fam == "gconv_split_pre"
+        head = (C.byref(q.d), *(q.planes if pre else (q.x.ptr,)), _p(q.w), C.c_int64(q.k * q.k * q.x.C * q.out.C), q.out.ptr)
+        if q.bnb:
+            self.op(q.lst, q.name, self.L.rd_gconv_split_pre_bnbwd if pre else self.L.rd_gconv_split_bnbwd, *head, *q.bnb, self.stream)
+        else:
+            # (no BatchNorm-backward sums from this epilogue: the caller keeps its reduce pass, as in the bf16 plans)
+            fn = {"gconv_split_pre": self.L.rd_gconv_split_pre, "gconv_split": self.L.rd_gconv_split, "gemm_taps_split": self.L.rd_gemm_taps_split}
+            self.op(q.lst, q.name, fn[q.fam], *head, C.c_void_p(0), 0, 0, *self._addend(q.addend), _p(q.stat), self.stream)
+
+    def _emit_bf16(self, q):
+        # (bf16 plans keep the separate BatchNorm-backward reduce pass: the same fusion in gconv_bf16's epilogue -- parity-green in
+        #  round 3 -- made the bf16-storage step 5 % SLOWER, 1790 -> 1697 samples/s: that kernel's epilogue is already its longest
+        #  phase, and the extra x loads sit on it)
+        self.op(q.lst, q.name, self.L.rd_gconv_bf16_t, self.dt, C.byref(q.d), q.x.ptr, _p(q.w), q.out.ptr, *(q.epilogue or (C.c_void_p(0), 0, 0)),
+                *self._addend(q.addend), _p(q.stat), self.stream)
+
+    def _emit_conv16(self, q):
+        self.op(q.lst, q.name, self.L.rd_conv16_split, C.byref(q.d), q.x.ptr, _p(q.w), q.out.ptr, *self._addend(q.addend), _p(q.stat), self.stream)
+
+    def _emit_gconv(self, q):
+        """rd_gconv_ws, its BatchNorm-backward instantiation (family gconv_bnb) and, with an epilogue (bias, act, columns), rd_gconv_fused."""
+        ws = self._gconv_ws(q.d, q.name)      # (plans the descriptor: table pin / tuner first)
+        head = (C.byref(q.d), q.x.ptr, _p(q.w), q.out.ptr)
+        if q.bnb:
+            # the BatchNorm behind this convolution's forward input takes its backward sums from this launch's epilogue:
+            # one pass over (dy, x) and one launch less per conv -> BN -> ReLU -> conv chain
+            self.op(q.lst, q.name, self.L.rd_gconv_bnbwd, *head, *q.bnb, _p(ws), self.stream)
+        elif q.epilogue:
+            self.op(q.lst, q.name, self.L.rd_gconv_fused, *head, *q.epilogue, *self._addend(q.addend), _p(ws), self.stream)
+        else:
+            self.op(q.lst, q.name, self.L.rd_gconv_ws, *head, *self._addend(q.addend), _p(q.stat), _p(ws), self.stream)
+
+    CONV_EMITTERS = {"wino": _emit_wino, "gconv_split_pre": _emit_pieces, "gconv_split": _emit_pieces, "gemm_taps_split": _emit_pieces,
+                     "gconv_bf16": _emit_bf16, "conv16_split": _emit_conv16, "gconv": _emit_gconv, "gconv_bnb": _emit_gconv}
+
+    def _launch_conv(self, lst, name, fam, d, x, w, out, k, addend=None, stat=None, planes=None, bnb=None, epilogue=None):
+        """One convolution launch of family fam (forward: x -> out with statistics; input gradient: dout -> dx with an addend or a
+        BatchNorm-backward tail; eval: with an epilogue), named name in lst and in self.meta."""
+        self.CONV_EMITTERS[fam](self, types.SimpleNamespace(lst=lst, name=name, fam=fam, d=d, x=x, w=w, out=out, k=k, addend=addend, stat=stat,
+                                                            planes=planes, bnb=bnb, epilogue=epilogue))
+        self.meta[name] = (fam, d)
+
+    def _operand(self, fam, w0, taps, rows, cols, flip):
+        """Packed weight operand of a launch of family fam -> (buffer, pack-job quad: 3 pieces / 2 bf16 / 1 fp32, None: Winograd's own job)."""
+        if fam == "wino":
+            self.L.rd_wino_packed_bytes.restype = C.c_int64
+            cout, cin = (cols, rows) if not flip else (rows, cols)
+            u = self.buf(int(self.L.rd_wino_packed_bytes(cout, cin, flip)) // 2, dtype=torch.bfloat16)
+            self.wino_jobs.append((w0, u, cout, cin, flip))
+            return u, None
+        if fam in self.PIECE_OPERAND:
+            return self.buf(3, taps, rows, cols, dtype=torch.bfloat16), 3
+        return self.buf(taps, rows, cols, dtype=torch.bfloat16 if self.bf16 else torch.float32), 2 if self.bf16 else 1
+
+    def conv_fwd(self, name, x, weights, k, stride, pad, out=None, kind="conv", lst=None):
+        """weights: list of (param, column offset), OIHW params except for kind "deconv" (CONV_KINDS).  Returns (raw Act, ctx)."""
+        assert kind in CONV_KINDS
+        lst = self.fwd if lst is None else lst
+        deconv = kind == "deconv"
+        assert not deconv or (len(weights) == 1 and weights[0][1] == 0)
+        cin, cout = x.C, sum(w.shape[1 if deconv else 0] for w, _ in weights)
+        d = self._desc(kind, False, x, cout, k, stride, pad, ldi=x.ld)[0]
+        if out is None:
+            out = self.act(x.N, d.Ho, d.Wo, cout)
+        d.ldo = out.ld
+        fam, fam_d = self._conv_families(kind, x, out, d, k, stride, pad, weights)
+        wp, quad_f = self._operand(fam, weights[0][0], k * k, cin, cout, 0)
+        wd, quad_d = self._operand(fam_d, weights[0][0], k * k, cout, cin, 1)
+        for w, off in weights:
+            o, i, kh, kw = w.shape
+            if deconv:
+                # the [Cin, Cout, k, k] weight read as the adjoint conv's OIHW weight (O = cin, I = cout): the forward is that conv's input
+                # gradient (transposed operand [slab][cin][cout]), the input gradient its forward (plain operand [slab][cout][cin])
+                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, 0, cin, 1, None, quad_f))
+                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, 0, i, 0, None, quad_d))
+                continue
+            if quad_f:
+                self.pack_jobs.append((w, wp, o, i, kh * kw, cout, off, i, 0, None, quad_f))
+            if quad_d:
+                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, off, cout, 1, None, quad_d))
+        if fam != "wino" and fam not in self.PIECE_OPERAND:
+            self._tune(d)
+        tiles = self._stat_tiles(fam, d, x)
+        if tiles < 0:
+            check(tiles, "rd_gconv_stat_tiles(%s)" % name)
+        stat = self.buf(tiles, 2, cout) if self.train else None
+        self.keep.append(d)
+        if fam == "wino" and self.L.rd_wino_supported(x.H, x.W, cin, cout, x.ld, out.ld) != 1:
+            raise RuntimeError("%s: planned as a Winograd layer, but the library does not serve %dx%d %d->%d with strides %d / %d"
+                               % (name, x.H, x.W, cin, cout, x.ld, out.ld))
+        self._launch_conv(lst, name, fam, d, x, wp, out, k, stat=stat, planes=self.pc_in(x, lst) if fam == "gconv_split_pre" else None)
+        self.taps[name] = out
+        ctx = dict(name=name, d=d, x=x, out=out, weights=weights, wd=wd, k=k, stride=stride, pad=pad, kind=kind,
+                   stat=stat, tiles=tiles, cin=cin, cout=cout, dgrad=fam_d)
+        return out, ctx
+
+    WGRAD_KERNELS = {      # family -> (workspace size, launch, slab reduction)
+        "wgrad": ("rd_wgrad_workspace_floats", "rd_wgrad", "rd_wgrad_reduce"),
+        "wgrad_split": ("rd_wgrad_split_workspace_floats", "rd_wgrad_split", "rd_wgrad_split_reduce"),
+        "wgrad_split_pre": ("rd_wgrad_split_workspace_floats", "rd_wgrad_split_pre", "rd_wgrad_split_reduce"),
+        "wgrad_bf16": ("rd_wgrad_bf16_workspace_floats", "rd_wgrad_bf16_t", "rd_wgrad_bf16_reduce")}
+
+    def _launch_wgrad(self, ctx, fam, dwd, operands, ws):
+        """The weight-gradient chain (wgrad + its slab reductions into the parameters' gradient views).  It gates nothing until the bucket
+        boundary: it runs on the wgrad stream, concurrently with the dgrad / BatchNorm chain that continues on the current stream."""
+        name, bf16 = ctx["name"], fam == "wgrad_bf16"
+        cur = self.streams.index(self._s) if self._s in self.streams else 0
+        wst = 2 if cur == 0 else cur
+        self.edge(self.bwd, name + ".fork_wgrad", cur, wst)
+        with self.on(wst):
+            self.op(self.bwd, name + ".wgrad", getattr(self.L, self.WGRAD_KERNELS[fam][1]), *((self.dt,) if bf16 else ()), C.byref(dwd), *operands,
+                    _p(ws), self.stream)
+            self.meta[name + ".wgrad"] = (fam, dwd)
+            here = self.streams.index(self._s)
+            for w, off in sorted(ctx["weights"], key=lambda t: t[1]):
+                o, i, kh, kw = w.shape
+                if self.batch_reduces:
+                    # the slab reductions are not needed before the segment's bucket boundary: they are collected per
+                    # stream and issued as ONE batched launch pair at the end of the segment (_flush_reduces)
+                    self._pending_reduces.setdefault(here, []).append((name, dwd, int(bf16), ws, self.grad_of(w), o, i, kh, kw, off))
+                else:
+                    self.op(self.bwd, name + ".wreduce", getattr(self.L, self.WGRAD_KERNELS[fam][2]), C.byref(dwd), _p(ws), _p(self.grad_of(w)),
+                            o, i, kh, kw, off, 0, self.stream)
+            if self.batch_reduces and len(self._pending_reduces.get(here, [])) >= self.reduce_batch_max:
+                self._flush_reduces(only=here)
+
     def conv_bwd(self, ctx, dout, need_dx=True, addend=None, dx=None, bnb=None):
         """Appends wgrad (+ reduce into the parameters' gradient views) and, optionally, dgrad.  Returns dx Act.
         bnb = dict(x=raw BatchNorm input Act, co=its coefficient dict, act=activation): this convolution's forward input was
-        act(BatchNorm(x)); when the library can (fp32, unsplit plan) the dgrad launch also emits that BatchNorm's backward sums
-        (rd_gconv_bnbwd) and self.bnb_out = (red, tiles) tells the caller to skip its reduce pass; else self.bnb_out = None."""
+        act(BatchNorm(x)); when the library can, the dgrad launch also emits that BatchNorm's backward sums (the *_bnbwd forms)
+        and self.bnb_out = (red, tiles) tells the caller to skip its reduce pass; else self.bnb_out = None."""
         self.bnb_out = None
         name, d, x = ctx["name"], ctx["d"], ctx["x"]
-        N, H, W, cin, cout, k = x.N, x.H, x.W, ctx["cin"], ctx["cout"], ctx["k"]
         deconv = ctx["kind"] == "deconv"
         if deconv:
             # a transposed convolution's weight gradient is its adjoint conv's, with dout as that conv's input and x as its output
             # gradient: the slabs [k*k][cout][cin] reduce straight into the [Cin, Cout, k, k] weight (convdesc.deconv_wgrad)
-            dwd = cd.deconv_wgrad(N, H, W, cin, cout, k, ld_dy=dout.ld, ld_x=x.ld)
-            w_in, w_dout = dout, x
+            dwd = cd.deconv_wgrad(x.N, x.H, x.W, x.C, ctx["cout"], ctx["k"], ld_dy=dout.ld, ld_x=x.ld)
+            operands = (dout.ptr, x.ptr)
         else:
             # wgrad uses the forward descriptor with dout's stride
             dwd = type(d)()
             C.memmove(C.byref(dwd), C.byref(d), C.sizeof(d))
             dwd.ldo = dout.ld
-            w_in, w_dout = x, dout
+            operands = (x.ptr, dout.ptr)
         self.keep.append(dwd)
-        # bf16 plans: the weight gradients run on the bf16 matrix cores as well (3x3 / 1x1 at both strides, UpProj 5x5); what the
-        # bf16 kernel cannot decompose keeps the fp32 kernel
-        # (32-wide MFMA tiles: the 16-channel layers are faster on the fp32 kernel -- 42 vs 55 us for the depth encoder's layer1)
-        wg_bf16 = (self.bf16 and os.environ.get("RD_WGRAD_BF16", "1") == "1" and min(cin, cout) >= int(os.environ.get("RD_WGRAD_BF16_MINC", "32"))
-                   and self.L.rd_wgrad_bf16_supported(C.byref(dwd)) == 1)
-        if self.storage == "bf16":
-            # bf16 tensors: only the bf16 weight-gradient kernel reads them (the 16-channel layers included: a half-empty
-            # 32-wide tile, but half the bytes and no conversion in its staging waves)
-            wg_bf16 = True
-            if self.L.rd_wgrad_bf16_supported(C.byref(dwd)) != 1:
-                raise NotImplementedError("bf16 storage: no bf16 weight-gradient decomposition for %s" % name)
-        # split plans: the 3x3 / stride-1 weight gradients with >= 64 channels run on the bf16 matrix cores as well (csrc/wgrad_split.hip:
-        # both operands split into three bf16 pieces while they are staged); same slabs, same deterministic reduction
-        wg_split = (self.split and not self.batch_reduces and os.environ.get("RD_WGRAD_SPLIT", "1") == "1"
-                    and self.L.rd_wgrad_split_supported(C.byref(dwd)) == 1)
-        f_ws, f_wgrad, f_reduce, fam = ((self.L.rd_wgrad_bf16_workspace_floats, self.L.rd_wgrad_bf16, self.L.rd_wgrad_bf16_reduce, "wgrad_bf16")
-                                        if wg_bf16 else
-                                        (self.L.rd_wgrad_split_workspace_floats, self.L.rd_wgrad_split, self.L.rd_wgrad_split_reduce, "wgrad_split")
-                                        if wg_split else (self.L.rd_wgrad_workspace_floats, self.L.rd_wgrad, self.L.rd_wgrad_reduce, "wgrad"))
-        nws = f_ws(C.byref(dwd))
+        wfam = self._wgrad_family(name, dwd, x, dout, deconv)
+        nws = getattr(self.L, self.WGRAD_KERNELS[wfam][0])(C.byref(dwd))
         if nws < 0:
             check(int(nws), "rd_wgrad_workspace_floats(%s)" % name)
         ws = self.buf(int(nws))
         # pre-split operands: both piece-plane sets are requested HERE, on the current stream in front of the dgrad / wgrad fork, so a
         # stand-alone split pass (an operand without a piece-writing producer) is ordered before both consumers
-        # (the weight gradient keeps splitting while it stages: its pre-split form measured 0.8-0.9x, profiles/r04_bench_wgrad_split.txt;
-        #  RD_WGRAD_PRE=1 opts in)
-        wg_pre = (wg_split and not deconv and os.environ.get("RD_WGRAD_PRE", "0") == "1" and self._pre_ok(x) and self._pre_ok(dout)
-                  and self.L.rd_wgrad_split_pre_supported(C.byref(dwd)) == 1)
-        sp_d0 = bool(ctx.get("split_dgrad"))
-        dg_pre = need_dx and sp_d0 and bool(ctx.get("pre_dgrad")) and self._pre_ok(dout)
-        yp = yplane = xp = xplane = None
-        if wg_pre or dg_pre:
-            yp, yplane = self.pc_in(dout, self.bwd)
-        if wg_pre:
-            xp, xplane = self.pc_in(x, self.bwd)
-        # the weight-gradient chain (wgrad + its slab reductions) gates nothing until the bucket boundary: it runs on the
-        # wgrad stream, concurrently with the dgrad / BatchNorm chain that continues on the current stream
-        cur = self.streams.index(self._s) if self._s in self.streams else 0
-        wst = 2 if cur == 0 else cur
-
-        def launch_wgrad():
-            self.edge(self.bwd, name + ".fork_wgrad", cur, wst)
-            with self.on(wst):
-                if wg_bf16:
-                    self.op(self.bwd, name + ".wgrad", self.L.rd_wgrad_bf16_t, self.dt, C.byref(dwd), w_in.ptr, w_dout.ptr, _p(ws), self.stream)
-                elif wg_pre:
-                    self.op(self.bwd, name + ".wgrad", self.L.rd_wgrad_split_pre, C.byref(dwd), xp, xplane, yp, yplane, _p(ws), self.stream)
-                else:
-                    self.op(self.bwd, name + ".wgrad", f_wgrad, C.byref(dwd), w_in.ptr, w_dout.ptr, _p(ws), self.stream)
-                self.meta[name + ".wgrad"] = ("wgrad_split_pre" if wg_pre else fam, dwd)
-                for w, off in sorted(ctx["weights"], key=lambda t: t[1]):
-                    o, i, kh, kw = w.shape
-                    if self.batch_reduces:
-                        # the slab reductions are not needed before the segment's bucket boundary: they are collected per
-                        # stream and issued as ONE batched launch pair at the end of the segment (_flush_reduces)
-                        self._pending_reduces.setdefault(self.streams.index(self._s), []).append(
-                            (name, dwd, 1 if wg_bf16 else 0, ws, self.grad_of(w), o, i, kh, kw, off))
-                    else:
-                        self.op(self.bwd, name + ".wreduce", f_reduce, C.byref(dwd), _p(ws), _p(self.grad_of(w)), o, i, kh, kw,
-                                off, 0, self.stream)
-                if self.batch_reduces and len(self._pending_reduces.get(self.streams.index(self._s), [])) >= self.reduce_batch_max:
-                    self._flush_reduces(only=self.streams.index(self._s))
-
+        dg_pre = need_dx and ctx["dgrad"] == "gconv_split_pre" and self._pre_ok(dout)
+        yplanes = self.pc_in(dout, self.bwd) if wfam == "wgrad_split_pre" or dg_pre else None
+        if wfam == "wgrad_split_pre":
+            operands = (*self.pc_in(x, self.bwd), *yplanes)
         # the weight-gradient chain is forked BEHIND the dgrad launch rather than beside it: both are MFMA-bound and gain nothing
         # from running together, whereas behind the dgrad the wgrad overlaps the memory-bound BatchNorm kernels that follow
         # (+1.4 % on the step; RD_WGRAD_AFTER_DGRAD=0 restores the side-by-side fork)
         late = os.environ.get("RD_WGRAD_AFTER_DGRAD", "1") == "1" and need_dx
         if not late:
-            launch_wgrad()
-        if not need_dx:
-            return None
+            self._launch_wgrad(ctx, wfam, dwd, operands, ws)
+        dx = self._launch_dgrad(ctx, dout, dx, addend, bnb, yplanes if dg_pre else None) if need_dx else None
+        if late:
+            self._launch_wgrad(ctx, wfam, dwd, operands, ws)
+        return dx
+
+    def _launch_dgrad(self, ctx, dout, dx, addend, bnb, yplanes):
+        """The input-gradient launch of conv_bwd; yplanes: dout's piece planes where conv_fwd planned the pre-split form."""
+        name, x = ctx["name"], ctx["x"]
         dx_owned = dx is None
         if dx is None:
-            dx = self.act(N, H, W, cin)
-        if deconv:
-            dd, zero_fill = cd.deconv_dgrad(N, H, W, cin, cout, k, ld_dy=dout.ld, ld_dx=dx.ld), False
-        elif ctx["kind"] == "upproj":
-            dd, zero_fill = cd.upproj_dgrad(N, H, W, cin, cout, ld_dy=dout.ld, ld_dx=dx.ld), False
-        else:
-            dd, zero_fill = cd.conv_dgrad(N, H, W, cin, cout, k, ctx["stride"], ctx["pad"], ld_dy=dout.ld, ld_dx=dx.ld)
+            dx = self.act(x.N, x.H, x.W, x.C)
+        dd, zero_fill = self._desc(ctx["kind"], True, x, ctx["cout"], ctx["k"], ctx["stride"], ctx["pad"], ld_dy=dout.ld, ld_dx=dx.ld)
         self.keep.append(dd)
         if zero_fill:
             assert dx.C == dx.ld, "zero-filled dgrad target must be a whole buffer"
@@ -591,104 +673,29 @@ class LateFusionPlan:
             else:
                 self.op(self.bwd, name + ".zero", self.L.rd_fill, dx.ptr, C.c_int64(dx.t.numel() * dx.t.element_size() // 4), C.c_float(0.0),
                         self.stream)
-        sp_d = bool(ctx.get("split_dgrad"))
-        # split plans (round 6): reduce-in-epilogue for the conv -> BN -> act -> conv chains, like rd_gconv_bnbwd on the fp32 plan (RD_SPLIT_BNB=0: off)
+        fam = self._confirm_dgrad(ctx, dd, dout, dx, yplanes is not None, zero_fill)
+        # The BatchNorm behind this convolution's forward input can take its backward sums from this launch's epilogue: rd_gconv_bnbwd on
+        # the fp32 plan; on split plans (round 6) reduce-in-epilogue for the conv -> BN -> act -> conv chains too (RD_SPLIT_BNB=0: off).
         # RD_SPLIT_BNB: "0" none, "1" all, or a comma list of kernel families: wino, pre (gconv_sp2), split (8-wave).  Measured on the step
-        # (profiles/r06_split_bnb_ab.txt): see the default below.
-        bnb_fam = "wino" if ctx.get("wino_dgrad") else "pre" if dg_pre else "split"
+        # (profiles/r06_split_bnb_ab.txt): see the default above.
+        can = bnb is not None and addend is None and not zero_fill and self.fuse_bn_bwd
         want = os.environ.get("RD_SPLIT_BNB", SPLIT_BNB_DEFAULT)
-        split_bnb = (bnb is not None and addend is None and not zero_fill and self.fuse_bn_bwd and self.split
-                     and (want == "1" or bnb_fam in want.split(",")) and dx.C % 4 == 0 and dx.ld % 4 == 0)
-        if ctx.get("wino_dgrad"):
-            # the input gradient of a Winograd layer: the same kernel on the flipped operand (channels swapped, taps rotated by 180 degrees)
-            if zero_fill or self.L.rd_wino_supported(H, W, cout, cin, dout.ld, dx.ld) != 1:
-                raise RuntimeError("%s: planned as a Winograd input gradient, but the library does not serve %dx%d %d->%d with strides %d / %d"
-                                   % (name, H, W, cout, cin, dout.ld, dx.ld))
-            self.meta[name + ".dgrad"] = ("wino", dd)
-            if split_bnb:
-                # the BatchNorm behind this convolution's forward input takes its backward sums from this launch's epilogue (one
-                # rd_bn_bwd_reduce_x_t pass over dx and x less per conv -> BN -> ReLU -> conv chain; VERDICT r5 item 2b, second half)
-                tiles = self.L.rd_wino_stat_tiles(N, H, W)
-                red = self.buf(tiles, 3, dx.C)
-                xb, co = bnb["x"], bnb["co"]
-                assert xb.M == dx.M and xb.C == dx.C
-                self.op(self.bwd, name + ".dgrad", self.L.rd_wino_conv3x3_bnbwd, dout.ptr, N, H, W, cout, dout.ld, _p(ctx["ud"]), dx.ptr, cin, dx.ld,
-                        xb.ptr, xb.ld, _p(co["mean"]), _p(co["scale"]), _p(co["shift"]), bnb["act"], _p(red), self.stream)
-                self.bnb_out = (red, tiles)
-            else:
-                self.op(self.bwd, name + ".dgrad", self.L.rd_wino_conv3x3, dout.ptr, N, H, W, cout, dout.ld, _p(ctx["ud"]), dx.ptr, cin, dx.ld,
-                        addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0, C.c_void_p(0), self.stream)
-            if late:
-                launch_wgrad()
-            return dx
-        if ctx.get("taps_dgrad"):
-            if self.L.rd_gemm_taps_split_supported(C.byref(dd)) != 1:
-                raise RuntimeError("%s: planned on rd_gemm_taps_split, but the library does not serve the final input-gradient descriptor" % name)
-            self.meta[name + ".dgrad"] = ("gemm_taps_split", dd)
-            self.op(self.bwd, name + ".dgrad", self.L.rd_gemm_taps_split, C.byref(dd), dout.ptr, _p(ctx["wd"]), C.c_int64(k * k * cin * cout), dx.ptr,
-                    C.c_void_p(0), 0, 0, addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
-                    C.c_void_p(0), self.stream)
-            if late:
-                launch_wgrad()
-            return dx
-        dg_pre = dg_pre and sp_d and self.L.rd_gconv_split_pre_supported(C.byref(dd)) == 1
-        if sp_d and not dg_pre and self.L.rd_gconv_split_supported(C.byref(dd)) != 1:
-            raise RuntimeError("%s: the input-gradient operand was packed as three bf16 pieces, but the library has neither a split plan for "
-                               "the final descriptor nor piece planes for its output-gradient tensor" % name)
-        self.meta[name + ".dgrad"] = ("gconv_split_pre" if dg_pre else "gconv_split" if sp_d else "gconv_bf16" if self.bf16 else "gconv", dd)
-        # (bf16 plans keep the separate BatchNorm-backward reduce pass: the same fusion in gconv_bf16's epilogue -- parity-green in
-        #  round 3 -- made the bf16-storage step 5 % SLOWER, 1790 -> 1697 samples/s: that kernel's epilogue is already its longest
-        #  phase, and the extra x loads sit on it)
-        if (dg_pre or sp_d) and split_bnb and self.L.rd_gconv_split_bnbwd_supported(C.byref(dd), 1 if dg_pre else 0) == 1:
-            tiles = (self.L.rd_gconv_split_pre_stat_tiles if dg_pre else self.L.rd_gconv_split_stat_tiles)(C.byref(dd))
-            red = self.buf(tiles, 3, dx.C)
-            xb, co = bnb["x"], bnb["co"]
-            assert xb.M == dx.M and xb.C == dx.C
-            if dg_pre:
-                self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_split_pre_bnbwd, C.byref(dd), yp, yplane, _p(ctx["wd"]), C.c_int64(k * k * cin * cout),
-                        dx.ptr, xb.ptr, xb.ld, _p(co["mean"]), _p(co["scale"]), _p(co["shift"]), bnb["act"], _p(red), self.stream)
-            else:
-                self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_split_bnbwd, C.byref(dd), dout.ptr, _p(ctx["wd"]), C.c_int64(k * k * cin * cout),
-                        dx.ptr, xb.ptr, xb.ld, _p(co["mean"]), _p(co["scale"]), _p(co["shift"]), bnb["act"], _p(red), self.stream)
-            self.bnb_out = (red, tiles)
-        elif dg_pre:
-            self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_split_pre, C.byref(dd), yp, yplane, _p(ctx["wd"]), C.c_int64(k * k * cin * cout), dx.ptr,
-                    C.c_void_p(0), 0, 0, addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
-                    C.c_void_p(0), self.stream)
-        elif sp_d:
-            # (no BatchNorm-backward sums from this epilogue: the caller keeps its reduce pass, as in the bf16 plans)
-            self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_split, C.byref(dd), dout.ptr, _p(ctx["wd"]), C.c_int64(k * k * cin * cout), dx.ptr,
-                    C.c_void_p(0), 0, 0, addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
-                    C.c_void_p(0), self.stream)
-        elif self.bf16:
-            self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_bf16_t, self.dt, C.byref(dd), dout.ptr, _p(ctx["wd"]), dx.ptr, C.c_void_p(0), 0, 0,
-                    addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
-                    C.c_void_p(0), self.stream)
-        elif self._c16_split(dd):
-            self.op(self.bwd, name + ".dgrad", self.L.rd_conv16_split, C.byref(dd), dout.ptr, _p(ctx["wd"]), dx.ptr,
-                    addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0, C.c_void_p(0), self.stream)
-            self.meta[name + ".dgrad"] = ("conv16_split", dd)
+        asked = "wino" if fam == "wino" else "pre" if yplanes is not None else "split"
+        split_bnb = can and self.split and (want == "1" or asked in want.split(",")) and dx.C % 4 == 0 and dx.ld % 4 == 0
+        if fam == "gconv":
+            can = can and self.L.rd_gconv_bnbwd_supported(C.byref(dd)) == 1
+        elif fam in ("gconv_split_pre", "gconv_split"):
+            can = split_bnb and self.L.rd_gconv_split_bnbwd_supported(C.byref(dd), 1 if fam == "gconv_split_pre" else 0) == 1
         else:
-            ws_d = self._gconv_ws(dd, name + ".dgrad")      # (plans the descriptor: table pin / tuner first)
-            fuse = (bnb is not None and addend is None and not zero_fill and self.fuse_bn_bwd
-                    and self.L.rd_gconv_bnbwd_supported(C.byref(dd)) == 1)
-            if fuse:
-                # the BatchNorm behind this convolution's forward input takes its backward sums from this launch's epilogue:
-                # one pass over (dy, x) and one launch less per conv -> BN -> ReLU -> conv chain
-                tiles = self.L.rd_gconv_stat_tiles_ws(C.byref(dd))
-                red = self.buf(tiles, 3, dx.C)
-                xb, co = bnb["x"], bnb["co"]
-                assert xb.M == dx.M and xb.C == dx.C
-                self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_bnbwd, C.byref(dd), dout.ptr, _p(ctx["wd"]), dx.ptr, xb.ptr, xb.ld,
-                        _p(co["mean"]), _p(co["scale"]), _p(co["shift"]), bnb["act"], _p(red), _p(ws_d), self.stream)
-                self.bnb_out = (red, tiles)
-                self.meta[name + ".dgrad"] = ("gconv_bnb", dd)      # (the BNB instantiation of the kernel: its own name in a trace)
-            else:
-                self.op(self.bwd, name + ".dgrad", self.L.rd_gconv_ws, C.byref(dd), dout.ptr, _p(ctx["wd"]), dx.ptr,
-                        addend.ptr if addend is not None else C.c_void_p(0), addend.ld if addend is not None else 0,
-                        C.c_void_p(0), _p(ws_d), self.stream)
-        if late:
-            launch_wgrad()
+            can = split_bnb and fam == "wino"
+        tail = None
+        if can:
+            tiles = self._stat_tiles(fam, dd, x)
+            red = self.buf(tiles, 3, dx.C)
+            assert bnb["x"].M == dx.M and bnb["x"].C == dx.C
+            tail, self.bnb_out = self._bnb_tail(bnb, red), (red, tiles)
+            fam = "gconv_bnb" if fam == "gconv" else fam      # (the BNB instantiation of the kernel: its own name in a trace)
+        self._launch_conv(self.bwd, name + ".dgrad", fam, dd, dout, ctx["wd"], dx, ctx["k"], addend=addend, planes=yplanes, bnb=tail)
         return dx
 
     def _flush_reduces(self, only=None):
@@ -724,18 +731,12 @@ class LateFusionPlan:
         """Eval-mode conv+BN(+act)(+residual) as ONE kernel: the BatchNorm scale gamma/sqrt(var+eps)
         is folded into the packed weights, its shift is the epilogue bias.  parts: [(conv weight, column offset, bn)]; kind: CONV_KINDS."""
         assert kind in CONV_KINDS
-        N, H, W, cin = x.N, x.H, x.W, x.C
         deconv = kind == "deconv"
-        cout = sum(w.shape[1 if deconv else 0] for w, _, _ in parts)
-        if deconv:
-            assert len(parts) == 1 and parts[0][1] == 0 and stride == 2 and pad == cd.deconv_pad(k)
-            d = cd.deconv_fwd(N, H, W, cin, cout, k, ldi=x.ld)
-        elif kind == "upproj":
-            d = cd.upproj_fwd(N, H, W, cin, cout, ldi=x.ld)
-        else:
-            d = cd.conv_fwd(N, H, W, cin, cout, k, stride, pad, ldi=x.ld)
+        assert not deconv or (len(parts) == 1 and parts[0][1] == 0)
+        cin, cout = x.C, sum(w.shape[1 if deconv else 0] for w, _, _ in parts)
+        d = self._desc(kind, False, x, cout, k, stride, pad, ldi=x.ld)[0]
         if out is None:
-            out = self.act(N, d.Ho, d.Wo, cout)
+            out = self.act(x.N, d.Ho, d.Wo, cout)
         d.ldo = out.ld
         wp = self.buf(k * k, cin, cout, dtype=torch.bfloat16 if self.bf16 else torch.float32)
         bias = self.buf(cout)
@@ -752,17 +753,8 @@ class LateFusionPlan:
             self.evalcoef_jobs.append((o, bn, sc, sh))       # all folded BatchNorms: ONE launch (see _finish_pack_jobs)
             self.pack_jobs.append((w, wp, o, i, kh * kw, cout, off, i, 0, scale[off:off + o], 2 if self.bf16 else 1))
         self.keep += [d, scale]
-        if self.bf16:
-            self.op(self.fwd, name, self.L.rd_gconv_bf16_t, self.dt, C.byref(d), x.ptr, _p(wp), out.ptr, _p(bias), act,
-                    cout if act_cols is None else act_cols, addend.ptr if addend is not None else C.c_void_p(0),
-                    addend.ld if addend is not None else 0, C.c_void_p(0), self.stream)
-            self.meta[name] = ("gconv_bf16", d)
-            return out
-        ws = self._gconv_ws(d, name)
-        self.op(self.fwd, name, self.L.rd_gconv_fused, C.byref(d), x.ptr, _p(wp), out.ptr, _p(bias), act,
-                cout if act_cols is None else act_cols, addend.ptr if addend is not None else C.c_void_p(0),
-                addend.ld if addend is not None else 0, _p(ws), self.stream)
-        self.meta[name] = ("gconv", d)
+        self._launch_conv(self.fwd, name, "gconv_bf16" if self.bf16 else "gconv", d, x, wp, out, k, addend=addend,
+                          epilogue=(_p(bias), act, cout if act_cols is None else act_cols))
         return out
 
     # ------------------------------------------------------------------ batch norm
@@ -784,20 +776,20 @@ class LateFusionPlan:
         """out = act(bn1(x1) [+ bn2(x2) | + x2])."""
         if out is None:
             out = self.act(x1.N, x1.H, x1.W, x1.C)
-        if self._pre_ok(out):
-            pcp, pcs = self.pc_out(out)
-            self.op(self.fwd, name, self.L.rd_bn_act_p, x1.ptr, x1.ld, _p(co1["scale"]), _p(co1["shift"]),
-                    x2.ptr if x2 is not None else C.c_void_p(0), x2.ld if x2 is not None else 0,
-                    _p(co2["scale"]) if co2 is not None else C.c_void_p(0), _p(co2["shift"]) if co2 is not None else C.c_void_p(0),
-                    out.ptr, out.ld, C.c_int64(x1.M), x1.C, act, pcp, pcs, self.stream)
-            self.taps[name] = out
-            return out
-        self.op(self.fwd, name, self.L.rd_bn_act_t, self.dt, x1.ptr, x1.ld, _p(co1["scale"]), _p(co1["shift"]),
-                x2.ptr if x2 is not None else C.c_void_p(0), x2.ld if x2 is not None else 0,
-                _p(co2["scale"]) if co2 is not None else C.c_void_p(0), _p(co2["shift"]) if co2 is not None else C.c_void_p(0),
-                out.ptr, out.ld, C.c_int64(x1.M), x1.C, act, self.stream)
+        c2 = co2 or {}      # (an identity residual has no coefficients: NULL)
+        self.op_pieces(self.fwd, name, "rd_bn_act", [out], x1.ptr, x1.ld, _p(co1["scale"]), _p(co1["shift"]), *self._addend(x2),
+                       _p(c2.get("scale")), _p(c2.get("shift")), out.ptr, out.ld, C.c_int64(x1.M), x1.C, act)
         self.taps[name] = out
         return out
+
+    def op_pieces(self, lst, name, kernel, outs, *args):
+        """One launch of a kernel pair <kernel>_p / <kernel>_t.  The _p form also writes the piece planes of its outputs outs (Acts): it
+        is taken when every output may carry planes, with (piece pointer, plane stride) appended per output; the _t form takes the
+        tensors' element type in front.  (pc_out registers a producer slot, so it is asked only where the _p form is taken.)"""
+        if all(self._pre_ok(a) for a in outs):
+            self.op(lst, name, getattr(self.L, kernel + "_p"), *args, *[v for a in outs for v in self.pc_out(a)], self.stream)
+        else:
+            self.op(lst, name, getattr(self.L, kernel + "_t"), self.dt, *args, self.stream)
 
     def bn_join_bwd(self, name, dy, y, act, x1, co1, x2=None, co2=None, dx2=None, lone=False, pre=None):
         """Backward of out = act(bn1(x1) [+ bn2(x2) | + x2]).  Returns (dx1, dx2 or g-if-identity-residual).
@@ -829,29 +821,17 @@ class LateFusionPlan:
                 dx2 = self.act(x2.N, x2.H, x2.W, Cc)
             b1, b2 = co1["bn"], co2["bn"]
             coef = self.buf(6 * Cc)
-            if self._pre_ok(dx1) and self._pre_ok(dx2):
-                p1, s1_ = self.pc_out(dx1)
-                p2, s2_ = self.pc_out(dx2)
-                self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_x2_p, dy.ptr, dy.ld, x1.ptr, x1.ld, x2.ptr, x2.ld, _p(red), tiles,
-                        _p(b1.weight), _p(co1["mean"]), _p(co1["invstd"]), _p(co1["scale"]), _p(co1["shift"]),
-                        _p(b2.weight), _p(co2["mean"]), _p(co2["invstd"]), _p(co2["scale"]), _p(co2["shift"]), act,
-                        _p(self.grad_of(b1.weight)), _p(self.grad_of(b1.bias)), _p(self.grad_of(b2.weight)), _p(self.grad_of(b2.bias)),
-                        _p(coef), dx1.ptr, dx1.ld, dx2.ptr, dx2.ld, C.c_int64(M), Cc, p1, s1_, p2, s2_, self.stream)
-                return dx1, dx2
-            self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_x2_t, self.dt, dy.ptr, dy.ld, x1.ptr, x1.ld, x2.ptr, x2.ld, _p(red), tiles,
-                    _p(b1.weight), _p(co1["mean"]), _p(co1["invstd"]), _p(co1["scale"]), _p(co1["shift"]),
-                    _p(b2.weight), _p(co2["mean"]), _p(co2["invstd"]), _p(co2["scale"]), _p(co2["shift"]), act,
-                    _p(self.grad_of(b1.weight)), _p(self.grad_of(b1.bias)), _p(self.grad_of(b2.weight)), _p(self.grad_of(b2.bias)),
-                    _p(coef), dx1.ptr, dx1.ld, dx2.ptr, dx2.ld, C.c_int64(M), Cc, self.stream)
+            self.op_pieces(self.bwd, name + ".bwd_apply", "rd_bn_bwd_apply_x2", [dx1, dx2], dy.ptr, dy.ld, x1.ptr, x1.ld, x2.ptr, x2.ld, _p(red), tiles,
+                           _p(b1.weight), _p(co1["mean"]), _p(co1["invstd"]), _p(co1["scale"]), _p(co1["shift"]),
+                           _p(b2.weight), _p(co2["mean"]), _p(co2["invstd"]), _p(co2["scale"]), _p(co2["shift"]), act,
+                           _p(self.grad_of(b1.weight)), _p(self.grad_of(b1.bias)), _p(self.grad_of(b2.weight)), _p(self.grad_of(b2.bias)),
+                           _p(coef), dx1.ptr, dx1.ld, dx2.ptr, dx2.ld, C.c_int64(M), Cc)
             return dx1, dx2
         # with no activation g == dy: skip the copy and let the apply pass read dy directly
         g = self.act(x1.N, x1.H, x1.W, Cc) if act != ACT_NONE else dy
-        if True:
-            self.op(self.bwd, name + ".bwd_reduce", self.L.rd_bn_bwd_reduce_t, self.dt, dy.ptr, dy.ld, y.ptr if y is not None else C.c_void_p(0),
-                    y.ld if y is not None else 0, x1.ptr, x1.ld, _p(co1["mean"]),
-                    x2.ptr if co2 is not None else C.c_void_p(0), x2.ld if co2 is not None else 0,
-                    _p(co2["mean"]) if co2 is not None else C.c_void_p(0), g.ptr if act != ACT_NONE else C.c_void_p(0), g.ld,
-                    C.c_int64(M), Cc, act, _p(red), self.stream)
+        self.op(self.bwd, name + ".bwd_reduce", self.L.rd_bn_bwd_reduce_t, self.dt, dy.ptr, dy.ld, *self._addend(y), x1.ptr, x1.ld, _p(co1["mean"]),
+                *self._addend(x2 if co2 else None), _p((co2 or {}).get("mean")), g.ptr if act != ACT_NONE else C.c_void_p(0), g.ld,
+                C.c_int64(M), Cc, act, _p(red), self.stream)
         dx1 = self.act(x1.N, x1.H, x1.W, Cc)
         self._bn_apply(name + ".bn1", g, x1, red, tiles, 1, co1, dx1)
         if co2 is not None:
@@ -864,28 +844,16 @@ class LateFusionPlan:
     def _bn_apply(self, name, g, x, red, tiles, which, co, dx):
         bn = co["bn"]
         coef = self.buf(3 * co["C"])
-        if self._pre_ok(dx):
-            pcp, pcs = self.pc_out(dx)
-            self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_p, g.ptr, g.ld, x.ptr, x.ld, _p(red), tiles, which,
-                    _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)),
-                    _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"], pcp, pcs, self.stream)
-            return
-        self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_t, self.dt, g.ptr, g.ld, x.ptr, x.ld, _p(red), tiles, which,
-                _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)),
-                _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"], self.stream)
+        self.op_pieces(self.bwd, name + ".bwd_apply", "rd_bn_bwd_apply", [dx], g.ptr, g.ld, x.ptr, x.ld, _p(red), tiles, which,
+                       _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)),
+                       _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"])
 
     def _bn_apply_x(self, name, dy, x, red, tiles, co, act, dx):
         bn = co["bn"]
         coef = self.buf(3 * co["C"])
-        if self._pre_ok(dx):
-            pcp, pcs = self.pc_out(dx)
-            self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_x_p, dy.ptr, dy.ld, x.ptr, x.ld, _p(red), tiles,
-                    _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(co["scale"]), _p(co["shift"]), act,
-                    _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)), _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"], pcp, pcs, self.stream)
-            return
-        self.op(self.bwd, name + ".bwd_apply", self.L.rd_bn_bwd_apply_x_t, self.dt, dy.ptr, dy.ld, x.ptr, x.ld, _p(red), tiles,
-                _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(co["scale"]), _p(co["shift"]), act,
-                _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)), _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"], self.stream)
+        self.op_pieces(self.bwd, name + ".bwd_apply", "rd_bn_bwd_apply_x", [dx], dy.ptr, dy.ld, x.ptr, x.ld, _p(red), tiles,
+                       _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(co["scale"]), _p(co["shift"]), act,
+                       _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)), _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"])
 
     # ------------------------------------------------------------------ network pieces
     def _stem(self, name, planes, strides, conv, bn, act, out_name):
@@ -914,13 +882,8 @@ class LateFusionPlan:
         Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
         pooled = self.act(N, Hp, Wp, cout)
         idx = self.buf(N, Hp, Wp, cout, dtype=torch.uint8)
-        if self._pre_ok(pooled):
-            pcp, pcs = self.pc_out(pooled)
-            self.op(self.fwd, name + ".bnact_pool", self.L.rd_bnact_maxpool_fwd_p, raw.ptr, _p(co["scale"]), _p(co["shift"]), act, N, Hc, Wc,
-                    cout, pooled.ptr, pooled.ld, _p(idx), pcp, pcs, self.stream)
-        else:
-            self.op(self.fwd, name + ".bnact_pool", self.L.rd_bnact_maxpool_fwd_t, self.dt, raw.ptr, _p(co["scale"]), _p(co["shift"]), act, N, Hc, Wc,
-                    cout, pooled.ptr, pooled.ld, _p(idx), self.stream)
+        self.op_pieces(self.fwd, name + ".bnact_pool", "rd_bnact_maxpool_fwd", [pooled], raw.ptr, _p(co["scale"]), _p(co["shift"]), act, N, Hc, Wc,
+                       cout, pooled.ptr, pooled.ld, _p(idx))
         self.taps[out_name] = pooled
         return pooled, dict(name=name, pl=pl, st=st, cin=cin, cout=cout, raw=raw, wp=wp, co=co, idx=idx, act=act, conv=conv,
                             pooled=pooled, Hc=Hc, Wc=Wc)
@@ -1160,13 +1123,7 @@ class LateFusionPlan:
         if self.depth_planes is None:
             self.x_bind.append((self.c_stem_d["pl"], self.c_stem_d["st"], 3, ndep))
         self._x_bound = xp           # base pointer the stems' plane tables point at (bind_input)
-        # The weight pack of everything but the stems runs on the (then idle) weight-gradient stream beside the stems and their pooling
-        # (_finish_pack_jobs): at the head of the step nothing else could overlap its ~0.2 ms.  Both encoder chains pick it up here.
-        self.pack_overlap = self.train and self.multi_stream and os.environ.get("RD_PACK_OVERLAP", "1") == "1"
-        if self.pack_overlap:
-            self.edge(self.fwd, "pack_join", 2, 0)
-            with self.on(1):
-                self.edge(self.fwd, "pack_join_depth", 2, 1)
+        self._pack_join(depth=True)
         self.blocks_rgb, self.blocks_d = [], []
         layers_rgb = [("layer1", m.layer1), ("layer2", m.layer2), ("layer3", m.layer3), ("layer4", m.layer4)]
         layers_d = [("layer1_depth", m.layer1_depth), ("layer2_depth", m.layer2_depth), ("layer3_depth", m.layer3_depth),
@@ -1195,33 +1152,44 @@ class LateFusionPlan:
         self.probe(self.fwd, "fwd_depth_encoder_end", 1)
         self.edge(self.fwd, "join_depth", 1, 0)
         # fusion 1x1 convs (no activation, models.py:652-657)
-        if not self.train:
-            yf = self.conv_bn_eval("conv_fusion", self.cat, [(m.conv_fusion.weight, 0, m.bn_fusion)], 1, 1, 0, ACT_NONE)
-            z = self.conv_bn_eval("conv2", yf, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
-            self.taps["bn_fusion"], self.taps["bn2"] = yf, z
-            dec_fwd, _ = self._decoder_ops(m.decoder)
-            for i, mod in enumerate((m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4), 1):
-                z, _ = dec_fwd("decoder.layer%d" % i, mod, z)
-            self._head(z)
-            self._finish_pack_jobs()
-            return
-        rf, self.c_fus = self.conv_fwd("conv_fusion", self.cat, [(m.conv_fusion.weight, 0)], 1, 1, 0)
-        self.co_fus = self.bn_coeffs("bn_fusion", m.bn_fusion, self.c_fus["stat"], self.c_fus["tiles"], rf.C, 0, rf.M)
-        self.yf = self.bn_act("bn_fusion", rf, self.co_fus, ACT_NONE)
-        r2, self.c_c2 = self.conv_fwd("conv2", self.yf, [(m.conv2.weight, 0)], 1, 1, 0)
-        self.co_c2 = self.bn_coeffs("bn2", m.bn2, self.c_c2["stat"], self.c_c2["tiles"], r2.C, 0, r2.M)
-        z = self.bn_act("bn2", r2, self.co_c2, ACT_NONE)
-        self.rf, self.r2 = rf, r2
-        # decoder
-        self.ups = []
-        dec_fwd, self.dec_bwd = self._decoder_ops(m.decoder)
-        for i, mod in enumerate((m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4), 1):
-            z, ctx = dec_fwd("decoder.layer%d" % i, mod, z)
-            self.ups.append(ctx)
-        self._head(z)
-        self._finish_pack_jobs()
+        if self.train:
+            self.rf, self.c_fus = self.conv_fwd("conv_fusion", self.cat, [(m.conv_fusion.weight, 0)], 1, 1, 0)
+            self.co_fus = self.bn_coeffs("bn_fusion", m.bn_fusion, self.c_fus["stat"], self.c_fus["tiles"], self.rf.C, 0, self.rf.M)
+            self.yf = self.bn_act("bn_fusion", self.rf, self.co_fus, ACT_NONE)
+        else:
+            self.yf = self.taps["bn_fusion"] = self.conv_bn_eval("conv_fusion", self.cat, [(m.conv_fusion.weight, 0, m.bn_fusion)], 1, 1, 0, ACT_NONE)
+        self._decode(self.yf)
         if self.train:
             self._build_backward()
+
+    def _pack_join(self, depth=False):
+        """The weight pack of everything but the stem(s) runs on the (then idle) weight-gradient stream beside the stems and their pooling
+        (_finish_pack_jobs): at the head of the step nothing else could overlap its ~0.2 ms.  The encoder chain(s) pick it up here."""
+        self.pack_overlap = self.train and self.multi_stream and os.environ.get("RD_PACK_OVERLAP", "1") == "1"
+        if self.pack_overlap:
+            self.edge(self.fwd, "pack_join", 2, 0)
+            if depth:
+                with self.on(1):
+                    self.edge(self.fwd, "pack_join_depth", 2, 1)
+
+    def _decode(self, x):
+        """conv2 / bn2 (no activation, models.py:295-296,655-657) -> the decoder's four layers -> head -> the weight-pack table."""
+        m = self.m
+        dec_fwd, self.dec_bwd = self._decoder_ops(m.decoder)
+        if self.train:
+            self.r2, self.c_c2 = self.conv_fwd("conv2", x, [(m.conv2.weight, 0)], 1, 1, 0)
+            self.co_c2 = self.bn_coeffs("bn2", m.bn2, self.c_c2["stat"], self.c_c2["tiles"], self.r2.C, 0, self.r2.M)
+            z = self.bn_act("bn2", self.r2, self.co_c2, ACT_NONE)
+        else:
+            z = self.taps["bn2"] = self.conv_bn_eval("conv2", x, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
+        ups = []
+        for i in (1, 2, 3, 4):
+            z, ctx = dec_fwd("decoder.layer%d" % i, getattr(m.decoder, "layer%d" % i), z)
+            ups.append(ctx)
+        if self.train:
+            self.ups = ups
+        self._head(z)
+        self._finish_pack_jobs()
 
     def _head(self, z):
         m, N = self.m, self.N
@@ -1302,43 +1270,38 @@ class LateFusionPlan:
             self.pack_table, self.pack_blocks = emit("pack_all", self.pack_jobs)
             emit_wino()
 
-    def _build_backward(self):
-        """Backward as four bucket-aligned segments (self.bwd_segments): every segment ends with all streams joined, so
-        it can be captured as its own hipGraph and its gradient bucket all-reduced while the next segment runs:
-          0: head, decoder, bn2/conv2, bn_fusion/conv_fusion      1: layer4 || layer4_depth
-          2: layer3 || layer3_depth                               3: layer2, layer1, stem || their depth counterparts
-        Inside a segment the RGB chain runs on stream 0, the depth chain on stream 1 and every weight-gradient chain of
-        the main stream on stream 2."""
-        m, N = self.m, self.N
-        z = self.z
+    def _end_segment(self, prefixes, side_streams=(1, 2), last=False):
+        """Close a backward segment (a gradient bucket): flush its slab reductions, then join the side streams into the main one -- or, with
+        segment_joins=False and not at the end of backward, record one event per side stream in self.segment_events instead."""
+        evs = []
+        self._flush_reduces()
+        if last:
+            for q in (0,) + tuple(side_streams):
+                self.probe(self.bwd, "bwd_end_stream%d" % q, q)
+        if last or self.segment_joins:
+            for q in side_streams:
+                self.edge(self.bwd, "join%d" % q, q, 0)
+        elif self.multi_stream:
+            for q in side_streams:
+                if (self.stream_mask >> (q - 1)) & 1:
+                    ev = self._event()
+                    self.op(self.bwd, "segment_end%d.record" % q, self.L.rd_event_record, ev, self.streams[q])
+                    evs.append(ev)
+        self.segment_events.append(evs)
+        begin = self.bwd_segments[-1][1] if self.bwd_segments else 0
+        self.bwd_segments.append((begin, len(self.bwd), prefixes))
+
+    def _head_bwd(self):
+        """Opens the backward pass: bilinear resize, then the head's input gradient on the main chain and its weight gradient (+ slab
+        reduction) on the weight-gradient stream beside the decoder's backward.  Returns the gradient of the decoder's output."""
+        m, N, z = self.m, self.N, self.z
         self.dpred = self.buf(N, 1, self.Ho, self.Wo)
         self.dx_dense = None
         self.bwd_segments = []
-
-        def end_segment(prefixes, last=False):
-            evs = []
-            self._flush_reduces()
-            if last:
-                for q in (0, 1, 2):
-                    self.probe(self.bwd, "bwd_end_stream%d" % q, q)
-            if last or self.segment_joins:
-                self.edge(self.bwd, "join1", 1, 0)
-                self.edge(self.bwd, "join2", 2, 0)
-            elif self.multi_stream:
-                for q in (1, 2):
-                    if (self.stream_mask >> (q - 1)) & 1:
-                        ev = self._event()
-                        self.op(self.bwd, "segment_end%d.record" % q, self.L.rd_event_record, ev, self.streams[q])
-                        evs.append(ev)
-            self.segment_events.append(evs)
-            begin = self.bwd_segments[-1][1] if self.bwd_segments else 0
-            self.bwd_segments.append((begin, len(self.bwd), prefixes))
-
         ddm = self.buf(N, z.H, z.W)
         self.op(self.bwd, "bilinear.bwd", self.L.rd_bilinear_bwd, _p(self.dpred), N, self.Ho, self.Wo, _p(ddm), z.H, z.W, self.stream)
         dz = self.act(N, z.H, z.W, z.C)
         ws = self.buf(int(self.L.rd_head_conv_bwd_workspace_floats(N, z.H, z.W, z.C)))
-        # input gradient on the main chain, weight gradient (+ slab reduction) on the weight-gradient stream beside the decoder's backward
         self.op(self.bwd, "conv3.dgrad", self.L.rd_head_conv_dgrad_t, self.dt, _p(m.conv3.weight), _p(ddm), N, z.H, z.W, z.C, dz.ptr, dz.ld,
                 self.stream)
         fork = os.environ.get("RD_HEAD_WGRAD_FORK", "1") == "1"
@@ -1347,10 +1310,25 @@ class LateFusionPlan:
         with self.on(2 if fork else 0):
             self.op(self.bwd, "conv3.wgrad", self.L.rd_head_conv_wgrad_t, self.dt, z.ptr, z.ld, _p(ddm), N, z.H, z.W, z.C,
                     _p(self.grad_of(m.conv3.weight)), _p(ws), self.stream)
+        return dz
+
+    def _decode_bwd(self):
+        """Backward of _decode: head, decoder layers, bn2 / conv2.  Returns conv2's input gradient."""
+        dz = self._head_bwd()
         for ctx in reversed(self.ups):
             dz = self.dec_bwd(ctx, dz)
         dr2, _ = self.bn_join_bwd("bn2", dz, None, ACT_NONE, self.r2, self.co_c2)
-        dyf = self.conv_bwd(self.c_c2, dr2)
+        return self.conv_bwd(self.c_c2, dr2)
+
+    def _build_backward(self):
+        """Backward as four bucket-aligned segments (self.bwd_segments): every segment ends with all streams joined, so
+        it can be captured as its own hipGraph and its gradient bucket all-reduced while the next segment runs:
+          0: head, decoder, bn2/conv2, bn_fusion/conv_fusion      1: layer4 || layer4_depth
+          2: layer3 || layer3_depth                               3: layer2, layer1, stem || their depth counterparts
+        Inside a segment the RGB chain runs on stream 0, the depth chain on stream 1 and every weight-gradient chain of
+        the main stream on stream 2."""
+        N, end_segment = self.N, self._end_segment
+        dyf = self._decode_bwd()
         drf, _ = self.bn_join_bwd("bn_fusion", dyf, None, ACT_NONE, self.rf, self.co_fus)
         dcat = self.act(N, self.cat.H, self.cat.W, self.cat.C)
         self.conv_bwd(self.c_fus, drf, dx=dcat)
@@ -1515,9 +1493,7 @@ class ResNetPlan(LateFusionPlan):
         x, self.c_stem = self._stem("conv1", [xp + 4 * hw * c for c in range(cin)], [cin * hw] * cin, m.conv1, m.bn1, ACT_RELU, "maxpool")
         self.x_bind = [(self.c_stem["pl"], self.c_stem["st"], 0, cin)]
         self._x_bound = xp
-        self.pack_overlap = self.train and self.multi_stream and os.environ.get("RD_PACK_OVERLAP", "1") == "1"
-        if self.pack_overlap:
-            self.edge(self.fwd, "pack_join", 2, 0)
+        self._pack_join()
         # the number of blocks per stage comes from the module: [2, 2, 2, 2] (resnet18) or [3, 4, 6, 3] (resnet34)
         self.stages = []
         for lname in ("layer1", "layer2", "layer3", "layer4"):
@@ -1527,79 +1503,26 @@ class ResNetPlan(LateFusionPlan):
                 ctxs.append(ctx)
             self.stages.append(ctxs)
         self.probe(self.fwd, "fwd_encoder_end", 0)
-        dec_fwd, self.dec_bwd = self._decoder_ops(m.decoder)
-        dec_layers = (m.decoder.layer1, m.decoder.layer2, m.decoder.layer3, m.decoder.layer4)
-        if not self.train:
-            z = self.conv_bn_eval("conv2", x, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
-            self.taps["bn2"] = z
-            for i, mod in enumerate(dec_layers, 1):
-                z, _ = dec_fwd("decoder.layer%d" % i, mod, z)
-            self._head(z)
-            self._finish_pack_jobs()
-            return
-        self.r2, self.c_c2 = self.conv_fwd("conv2", x, [(m.conv2.weight, 0)], 1, 1, 0)
-        self.co_c2 = self.bn_coeffs("bn2", m.bn2, self.c_c2["stat"], self.c_c2["tiles"], self.r2.C, 0, self.r2.M)
-        z = self.bn_act("bn2", self.r2, self.co_c2, ACT_NONE)
-        self.ups = []
-        for i, mod in enumerate(dec_layers, 1):
-            z, ctx = dec_fwd("decoder.layer%d" % i, mod, z)
-            self.ups.append(ctx)
-        self._head(z)
-        self._finish_pack_jobs()
-        self._build_backward()
+        self._decode(x)
+        if self.train:
+            self._build_backward()
 
     def _build_backward(self):
         """Four bucket-aligned segments, each ending with the weight-gradient stream joined (self.bwd_segments):
           0: head, decoder, bn2 / conv2     1: layer4     2: layer3     3: layer2, layer1, stem"""
-        m, N, z = self.m, self.N, self.z
-        self.dpred = self.buf(N, 1, self.Ho, self.Wo)
-        self.dx_dense = None
-        self.bwd_segments = []
-
-        def end_segment(prefixes, last=False):
-            evs = []
-            self._flush_reduces()
-            if last:
-                for q in (0, 2):
-                    self.probe(self.bwd, "bwd_end_stream%d" % q, q)
-            if last or self.segment_joins:
-                self.edge(self.bwd, "join2", 2, 0)
-            elif self.multi_stream and (self.stream_mask >> 1) & 1:
-                ev = self._event()
-                self.op(self.bwd, "segment_end2.record", self.L.rd_event_record, ev, self.streams[2])
-                evs.append(ev)
-            self.segment_events.append(evs)
-            begin = self.bwd_segments[-1][1] if self.bwd_segments else 0
-            self.bwd_segments.append((begin, len(self.bwd), prefixes))
-
-        ddm = self.buf(N, z.H, z.W)
-        self.op(self.bwd, "bilinear.bwd", self.L.rd_bilinear_bwd, _p(self.dpred), N, self.Ho, self.Wo, _p(ddm), z.H, z.W, self.stream)
-        dz = self.act(N, z.H, z.W, z.C)
-        ws = self.buf(int(self.L.rd_head_conv_bwd_workspace_floats(N, z.H, z.W, z.C)))
-        self.op(self.bwd, "conv3.dgrad", self.L.rd_head_conv_dgrad_t, self.dt, _p(m.conv3.weight), _p(ddm), N, z.H, z.W, z.C, dz.ptr, dz.ld,
-                self.stream)
-        fork = os.environ.get("RD_HEAD_WGRAD_FORK", "1") == "1"
-        if fork:
-            self.edge(self.bwd, "conv3.fork_wgrad", 0, 2)
-        with self.on(2 if fork else 0):
-            self.op(self.bwd, "conv3.wgrad", self.L.rd_head_conv_wgrad_t, self.dt, z.ptr, z.ld, _p(ddm), N, z.H, z.W, z.C,
-                    _p(self.grad_of(m.conv3.weight)), _p(ws), self.stream)
-        for ctx in reversed(self.ups):
-            dz = self.dec_bwd(ctx, dz)
-        dr2, _ = self.bn_join_bwd("bn2", dz, None, ACT_NONE, self.r2, self.co_c2)
-        g = self.conv_bwd(self.c_c2, dr2)
-        end_segment(("conv2", "bn2", "decoder", "conv3"))
+        g = self._decode_bwd()
+        self._end_segment(("conv2", "bn2", "decoder", "conv3"), side_streams=(2,))
         self.probe(self.bwd, "bwd_encoder_begin", 0)
         for stage in (3, 2):
             for ctx in reversed(self.stages[stage]):
                 g = self._block_bwd(ctx, g)
-            end_segment(("layer%d" % (stage + 1),))
+            self._end_segment(("layer%d" % (stage + 1),), side_streams=(2,))
         for stage in (1, 0):
             for ctx in reversed(self.stages[stage]):
                 g = self._block_bwd(ctx, g)
         # nobody asks an input gradient of this stem: on split plans its BatchNorm apply pass rides in the weight gradient's staging waves
         self._stem_bwd(self.c_stem, g)
-        end_segment(("conv1", "bn1", "layer1", "layer2"), last=True)
+        self._end_segment(("conv1", "bn1", "layer1", "layer2"), last=True, side_streams=(2,))
 
 
 class ModulePlan(LateFusionPlan):
