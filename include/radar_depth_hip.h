@@ -673,6 +673,45 @@ int rd_uniform_sparsify(const float* depth, int64_t depth_stride, int32_t B, int
                         const double* draws, uint64_t seed, uint64_t frame0, void* workspace, float* out, int64_t out_stride,
                         uint8_t* mask, void* stream);
 
+/* The validation comparison rows (csrc/visualize.hip): the reference's merge_into_row / merge_into_row_with_gt / colored_depthmap
+ * (utils.py:114-153) as its save_image's astype('uint8') leaves them.  Per frame one row of k = (rgb ? 1 : 0) + n_planes panels side by
+ * side, packed HWC uint8: row y of frame b starts at out + b * frame_stride + y * row_pitch (BYTES; no alignment is asked of either
+ * or of out) and is 3*k*W bytes long; no other byte is written, so a row can be rendered into a slice of a taller or wider canvas.
+ *   rgb      fp32 [B][3][H*W], frame b `rgb_stride` elements after frame b-1 (inputs[:, :3] of a [B,4,H,W] tensor: 4*H*W); values in
+ *            0..1; panel byte = trunc(255 * x), the product in float32.  May be NULL (a lone colored_depthmap): no rgb panel then.
+ *   planes   n_planes (1..3) HOST pointers to fp32 device planes [B][H*W] with their batch strides in elements (plane_strides).
+ *   range    NULL: every frame's d_min / d_max are the float32 minimum / maximum over all of that frame's planes together (frames are
+ *            never pooled), found on the device and kept there (workspace: rd_render_workspace_bytes(B) bytes, 8-byte aligned).
+ *            Otherwise two HOST doubles [d_min, d_max] for every frame; as numpy does with Python floats, d_min is rounded to float32
+ *            and the divisor is the float64 difference rounded to float32.  workspace may then be NULL.
+ *   table    259 x 3 bytes on the device: rows 0..255 the colours, 256 under, 257 over, 258 bad (radar_depth_amd/viridis_lut.json).
+ * Colour of a depth pixel d: rel = (d - d_min) / (d_max - d_min) in float32 with a correctly rounded division, xa = rel * 256;
+ * xa == 256 -> row 255, xa < 0 -> under, xa >= 256 (+inf too) -> over, NaN (0/0: every plane one value) -> bad, else row trunc(xa).
+ * NaN or inf INSIDE the planes is outside the contract: such a pixel gets a table colour, the frame-wide NaN of numpy's min is not
+ * reproduced.  At most three operations on `stream` whatever B and n_planes are (one memset and two launches; one launch with a given
+ * range); no allocation, no host synchronisation; integer atomics only, so the result is bit-reproducible.
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_EVIS_NULL     a null pointer (rgb may be null; workspace may be null when range is given)
+ *   RD_EVIS_RANGE    B, H or W outside 1..65535, or H*W >= 2^30
+ *   RD_EVIS_PLANES   n_planes outside 1..3
+ *   RD_EVIS_STRIDE   a plane's batch stride below H*W, or rgb's below 3*H*W
+ *   RD_EVIS_PITCH    row_pitch below 3*k*W, or frame_stride below H*row_pitch
+ *   RD_EVIS_NAN      NaN in the given range
+ *   RD_EVIS_OVERLAP  out (its whole extent) shares memory with an input
+ * rd_render_workspace_bytes returns RD_EVIS_RANGE for a B the call rejects. */
+#define RD_EVIS_NULL (-27)
+#define RD_EVIS_RANGE (-28)
+#define RD_EVIS_PLANES (-29)
+#define RD_EVIS_STRIDE (-30)
+#define RD_EVIS_PITCH (-31)
+#define RD_EVIS_NAN (-32)
+#define RD_EVIS_OVERLAP (-33)
+int64_t rd_render_workspace_bytes(int32_t B);
+int rd_render_rows(const float* rgb, int64_t rgb_stride, const float* const* planes, const int64_t* plane_strides, int32_t n_planes,
+                   int32_t B, int32_t H, int32_t W, const double* range, void* workspace, const uint8_t* table, uint8_t* out,
+                   int64_t frame_stride, int64_t row_pitch, void* stream);
+
 /* NCHW [N,C,H,W] (channel c0..c0+C of Ctot) <-> NHWC helpers for module-level tests */
 int rd_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

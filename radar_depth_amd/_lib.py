@@ -17,6 +17,8 @@ RD_ERADAR_NULL, RD_ERADAR_RANGE, RD_ERADAR_NRADAR, RD_ERADAR_NLIDAR, RD_ERADAR_F
 # ... and of the lidar sparsifiers
 RD_ESPARSE_NULL, RD_ESPARSE_RANGE, RD_ESPARSE_PIXELS, RD_ESPARSE_STRIDE, RD_ESPARSE_SAMPLES, RD_ESPARSE_MAXDEPTH = -20, -21, -22, -23, -24, -25
 RD_ESPARSE_OVERLAP = -26
+# ... and of the comparison-row renderer
+RD_EVIS_NULL, RD_EVIS_RANGE, RD_EVIS_PLANES, RD_EVIS_STRIDE, RD_EVIS_PITCH, RD_EVIS_NAN, RD_EVIS_OVERLAP = -27, -28, -29, -30, -31, -32, -33
 
 
 class RdPhase(C.Structure):
@@ -67,7 +69,7 @@ def lib():
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
                      "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats",
-                     "rd_lidar_sparsify_workspace_bytes"):
+                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
         # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
@@ -86,7 +88,10 @@ def lib():
                            ("rd_lidar_sparsify_workspace_bytes", [C.c_int32] * 3),
                            ("rd_lidar_radar_sparsify", [vp, C.c_int64, vp, C.c_int64] + [C.c_int32] * 3 + [vp, vp, C.c_int64, vp]),
                            ("rd_uniform_sparsify", [vp, C.c_int64] + [C.c_int32] * 3 + [C.c_int64, C.c_double, vp, C.c_uint64, C.c_uint64, vp, vp,
-                                                                                      C.c_int64, vp, vp])):
+                                                                                      C.c_int64, vp, vp]),
+                           # the comparison rows (csrc/visualize.hip)
+                           ("rd_render_workspace_bytes", [C.c_int32]),
+                           ("rd_render_rows", [vp, C.c_int64, vp, vp] + [C.c_int32] * 4 + [vp] * 4 + [C.c_int64, C.c_int64, vp])):
             if hasattr(_lib, name):
                 getattr(_lib, name).argtypes = args
     return _lib

@@ -1,11 +1,24 @@
-"""Counterpart of the reference's utils.py for the hot path: the argparse flag surface (utils.py:16-74) and the
-learning-rate schedule (utils.py:85-89).  save_checkpoint (utils.py:77-82) keeps the wire format; visualisation helpers are outside the path."""
+"""Counterpart of the reference's utils.py: the argparse flag surface (utils.py:16-74), the two learning-rate schedules
+(utils.py:85-102), save_checkpoint (utils.py:77-82; keeps the wire format) and the validation comparison images (utils.py:114-162).
+
+The comparison images are rendered on the GPU (csrc/visualize.hip behind rd_render_rows): ``merge_into_row``,
+``merge_into_row_with_gt`` and ``colored_depthmap`` take device tensors and return uint8 device tensors holding exactly the bytes the
+reference's ``save_image`` hands to Pillow, bit for bit, without a host copy or a synchronisation; ``ComparisonImage`` is a preallocated
+canvas whose rows are rendered in place and read back once.  The one difference in type: ``colored_depthmap`` returns uint8 where the
+reference returns the float64 ``255 * cmap(...)`` -- the result is what ``save_image``'s ``astype('uint8')`` makes of it.  The colour table
+(viridis, 259 x 3 uint8) ships as data (viridis_lut.json); neither matplotlib nor Pillow is needed to import this module or to render,
+Pillow only inside ``save_image``.  Not reproduced: NaN / inf inside the planes (numpy's min would make the whole frame NaN), rgb
+outside 0..1, and a range of which only one end is given."""
 import argparse
+import ctypes
+import json
 import os
 import shutil
 
+import numpy as np
 import torch
 
+from ._lib import check, current_stream, lib, ptr
 from .model.models import Decoder
 
 MODEL_NAMES = ['resnet18', 'resnet34', 'resnet50', 'resnet18_new', 'resnet18_latefusion', 'resnet18_multistage',
@@ -86,3 +99,158 @@ def adjust_learning_rate(optimizer, epoch, lr_init):
     else:
         optimizer.set_lr(lr)
     return lr
+
+
+def adjust_learning_rate_new(optimizer, epoch, lr_init):
+    """The reference's explicit schedule (utils.py:93-102): lr_init up to epoch 6, 0.1 * lr_init up to epoch 15, 0.01 * lr_init after;
+    works on torch optimizers and on radar_depth_amd.main.HipTrainStep."""
+    if epoch <= 6:
+        lr = lr_init
+    elif epoch <= 15:
+        lr = 0.1 * lr_init
+    else:
+        lr = 0.01 * lr_init
+    if hasattr(optimizer, "param_groups"):
+        for group in optimizer.param_groups:
+            group['lr'] = lr
+    else:
+        optimizer.set_lr(lr)
+    return lr
+
+
+# ---- the validation comparison images (utils.py:114-162) on the GPU
+
+_TABLE_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "viridis_lut.json")
+_tables = {}
+
+
+def viridis_table():
+    """uint8 [259,3] numpy array: trunc(255 * viridis._lut[:, :3]) -- rows 0..255 the colours, 256 under, 257 over, 258 bad."""
+    if "host" not in _tables:
+        with open(_TABLE_PATH) as fh:
+            t = np.array(json.load(fh)["rgb"], dtype=np.uint8)
+        assert t.shape == (259, 3), "viridis_lut.json: 259 rows of 3 bytes"
+        _tables["host"] = t
+    return _tables["host"]
+
+
+def _device_table(device):
+    """The table on `device`, uploaded once."""
+    key = (device.type, device.index)
+    if key not in _tables:
+        _tables[key] = torch.from_numpy(viridis_table().copy()).to(device)
+    return _tables[key]
+
+
+def _frames(t, channels, what):
+    """fp32 [B,channels,H,W] on the GPU (or one frame without the batch axis), every frame contiguous, any batch stride ->
+    (tensor as [B,channels,H,W], batch stride in elements)."""
+    assert torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32, what + ": a float32 tensor on the GPU"
+    if t.dim() == 3 or (t.dim() == 2 and channels == 1):
+        t = t.reshape((1, channels) + tuple(t.shape[-2:])) if t.dim() == 2 else t.unsqueeze(0)
+    assert t.dim() == 4 and t.shape[1] == channels and t.numel() > 0, "%s: [B,%d,H,W]" % (what, channels)
+    B, _, h, w = t.shape
+    assert (w == 1 or t.stride(3) == 1) and (h == 1 or t.stride(2) == w) and (channels == 1 or t.stride(1) == h * w), \
+        what + ": every frame must be contiguous"
+    return t, (t.stride(0) if B > 1 else channels * h * w)
+
+
+def _render(rgb, planes, d_range, out, squeeze):
+    planes = [_frames(p, 1, "depth plane") for p in planes]
+    B, _, h, w = planes[0][0].shape
+    dev = planes[0][0].device
+    k = len(planes) + (rgb is not None)
+    rgb_stride = 0
+    if rgb is not None:
+        rgb, rgb_stride = _frames(rgb, 3, "input")
+        assert tuple(rgb.shape) == (B, 3, h, w) and rgb.device == dev, "input: [B,3,H,W] like the depth planes"
+    for p, _ in planes:
+        assert tuple(p.shape) == (B, 1, h, w) and p.device == dev, "depth planes: one shape, one device"
+    shape = (h, k * w, 3) if squeeze and B == 1 else (B, h, k * w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    assert torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == dev and tuple(out.shape) == shape, \
+        "out: uint8 %s on the planes' device" % (shape,)
+    o4 = out if out.dim() == 4 else out.unsqueeze(0)
+    assert o4.stride(3) == 1 and o4.stride(2) == 3, "out: packed pixels (a row may have any pitch, a frame any stride)"
+    pitch = o4.stride(1) if h > 1 else 3 * k * w
+    frame_stride = o4.stride(0) if B > 1 else h * pitch
+    L = lib()
+    n = len(planes)
+    ptrs = (ctypes.c_void_p * n)(*[p.data_ptr() for p, _ in planes])
+    strides = (ctypes.c_int64 * n)(*[s for _, s in planes])
+    rng = work = None
+    if d_range is not None:
+        rng = (ctypes.c_double * 2)(float(d_range[0]), float(d_range[1]))
+    else:
+        # (a batch size the library rejects gives a negative size here; the call that follows reports it)
+        work = torch.empty(max(int(L.rd_render_workspace_bytes(B)), 16), dtype=torch.uint8, device=dev)
+    check(L.rd_render_rows(ptr(rgb), rgb_stride, ptrs, strides, n, B, h, w, rng, ptr(work), ptr(_device_table(dev)), ptr(out), frame_stride,
+                           pitch, current_stream()), "rd_render_rows")
+    return out
+
+
+def colored_depthmap(depth, d_min=None, d_max=None):
+    """The viridis image of a depth map: depth fp32 [H,W] -> uint8 [H,W,3], or [B,1,H,W] -> [B,H,W,3], on the GPU.  Without a range
+    every frame is scaled by its own minimum and maximum (found on the device; they never reach the host); with ``d_min`` and ``d_max``
+    (Python numbers, both or neither) pixels below the range take the first colour, pixels above it the last, and ``d_min == d_max``
+    gives first / last / black for pixels below / above / on it, as matplotlib does.  Returns uint8 where the reference returns the
+    float64 ``255 * cmap(...)``: the bytes are what its ``save_image`` makes of that."""
+    if (d_min is None) != (d_max is None):
+        raise ValueError("colored_depthmap: d_min and d_max are given together or not at all")
+    assert torch.is_tensor(depth) and depth.dim() in (2, 4), "colored_depthmap: depth [H,W] or [B,1,H,W]"
+    out = _render(None, [depth], None if d_min is None else (d_min, d_max), None, False)
+    return out[0] if depth.dim() == 2 else out
+
+
+def merge_into_row(input, depth_target, depth_pred, out=None):
+    """[rgb | target | prediction] side by side (modality rgb): input fp32 [B,3,H,W] in 0..1, the depth maps fp32 [B,1,H,W], all on
+    the GPU, each frame contiguous with any batch stride.  Returns uint8 [H,3W,3] for B = 1 (the reference's shape; it asserts B = 1)
+    and [B,H,3W,3] otherwise, every frame coloured by its own range over both depth maps.  ``out``: such a tensor to render into --
+    rows may have any pitch and frames any stride (``ComparisonImage.row(i)``); bytes outside the rows are not touched.
+    Queued on the current stream; nothing synchronises."""
+    return _render(input, [depth_target, depth_pred], None, out, True)
+
+
+def merge_into_row_with_gt(input, depth_input, depth_target, depth_pred, out=None):
+    """[rgb | sparse input depth | target | prediction] (modality rgbd): as ``merge_into_row`` with a fourth panel;
+    ``inputs[:, :3]`` and ``inputs[:, 3:4]`` of one [B,4,H,W] tensor are taken as they are, without a copy."""
+    return _render(input, [depth_input, depth_target, depth_pred], None, out, True)
+
+
+def add_row(img_merge, row):
+    """The reference's vstack: ``torch.cat`` along the rows for device tensors, ``np.vstack`` for arrays."""
+    if torch.is_tensor(img_merge):
+        return torch.cat([img_merge, row], dim=0)
+    return np.vstack([img_merge, row])
+
+
+class ComparisonImage:
+    """A preallocated device canvas of ``rows`` comparison rows, each ``height`` x ``panels * width`` pixels:
+        canvas = ComparisonImage(8, H, W, 4)
+        merge_into_row_with_gt(rgb, depth, target, pred, out=canvas.row(i))        # nothing is copied or concatenated
+        canvas.save(filename)                                                       # the one readback"""
+
+    def __init__(self, rows, height, width, panels, device="cuda"):
+        assert rows >= 1 and height >= 1 and width >= 1 and 2 <= panels <= 4
+        self.rows, self.height, self.width, self.panels = rows, height, width, panels
+        self.image = torch.zeros((rows * height, panels * width, 3), dtype=torch.uint8, device=device)
+
+    def row(self, i):
+        """uint8 [height, panels*width, 3]: the view to pass as ``out``."""
+        assert 0 <= i < self.rows
+        return self.image[i * self.height:(i + 1) * self.height]
+
+    def numpy(self):
+        return self.image.cpu().numpy()
+
+    def save(self, filename):
+        save_image(self.image, filename)
+
+
+def save_image(img_merge, filename):
+    """Write a comparison image: a uint8 device tensor (one readback) or, as in the reference, any numpy array (cast to uint8)."""
+    from PIL import Image
+    if torch.is_tensor(img_merge):
+        img_merge = img_merge.cpu().numpy()
+    Image.fromarray(img_merge.astype('uint8')).save(filename)
