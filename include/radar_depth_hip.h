@@ -227,7 +227,11 @@ int rd_gconv_trace_read(unsigned long long* host, int n_wg);
  * `d` is the FORWARD descriptor (in = forward input, "out" geometry = dout).  slabs is a
  * workspace of rd_wgrad_workspace_floats(d) floats; the result is reduced deterministically
  * into OIHW gradient tensors by rd_wgrad_reduce.  Replaces the weight half of
- * convolution_backward (autograd of models.py:96-112,203-206; 50% of the reference CPU step). */
+ * convolution_backward (autograd of models.py:96-112,203-206; 50% of the reference CPU step).
+ * in / dout may be channel slices of wider NHWC buffers (ldi >= Cin, ldo >= Cout; the other channels are never read).  Every
+ * weight-gradient entry point and query (rd_wgrad*, rd_wgrad_split*, rd_wgrad_bf16*) refuses, before anything is launched: a
+ * channel stride below the channel count, a tensor or slab base that is not 16-byte aligned, and reduction columns
+ * [co_off, co_off + O) outside [0, Cout). */
 int64_t rd_wgrad_workspace_floats(const RdConvDesc* d);
 int rd_wgrad(const RdConvDesc* d, const float* in, const float* dout, float* slabs, void* stream);
 /* grad_oihw[o][i][kh][kw] (+)= sum over slabs; o covers packed columns [co_off, co_off+O).

@@ -116,6 +116,20 @@ static inline bool piece_planes_ok(const void* pieces, int64_t piece_elems, int6
            piece_elems % 8 == 0;
 }
 
+// The argument checks that every weight-gradient entry point and query shares (rd_wgrad*, rd_wgrad_split*, rd_wgrad_bf16*, their
+// *_supported / *_workspace_floats / reduce forms), all made on the host before anything is launched:
+//  - the operands are channel slices of wider NHWC buffers, so a channel stride must cover the channel count;
+//  - every staging path moves 16-byte words (global_load_lds_dwordx4, buffer_load_b128, float4), so the tensor bases are 16-byte aligned;
+//  - a reduction writes packed columns [co_off, co_off + O) of the descriptor's Cout.
+static inline bool wgrad_strides_ok(const RdConvDesc& d) { return d.ldi >= d.Cin && d.ldo >= d.Cout; }
+static inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+#define RD_CHECK_WGRAD_STRIDES(d_, who_)                                                                                              \
+    RD_CHECK_ARG(rd::wgrad_strides_ok(d_), "%s: channel stride below the channel count (ldi %d, Cin %d; ldo %d, Cout %d)", who_, (d_).ldi, \
+                 (d_).Cin, (d_).ldo, (d_).Cout)
+#define RD_CHECK_WGRAD_COLS(d_, O_, co_off_, who_)                                                                                    \
+    RD_CHECK_ARG((co_off_) >= 0 && (O_) >= 0 && (int64_t)(co_off_) + (O_) <= (d_).Cout, "%s: columns [%d, %d + %d) outside Cout %d", who_, (co_off_), \
+                 (co_off_), (O_), (d_).Cout)
+
 int num_cus();
 // conv16.hip: the 16 -> 16 channel 3x3 / stride-1 convolutions on the 16x16x4 fp32 MFMA (dispatched from gconv.hip's plans)
 bool conv16_eligible(const RdConvDesc& d);

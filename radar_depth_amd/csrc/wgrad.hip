@@ -794,6 +794,7 @@ static bool upproj_split(const RdConvDesc& d) {
 static int plan_any_uncached(const RdConvDesc& d, WgradPlan& pl);
 // plans are a pure function of the descriptor: cached (the tile search would otherwise run on every launch of every step)
 static int plan_any(const RdConvDesc& d, WgradPlan& pl) {
+    RD_CHECK_WGRAD_STRIDES(d, "wgrad");
     static std::mutex mu;
     static std::unordered_map<std::string, WgradPlan> cache;
     std::string key(reinterpret_cast<const char*>(&d), sizeof(RdConvDesc));
@@ -881,6 +882,8 @@ extern "C" int64_t rd_wgrad_workspace_floats(const RdConvDesc* d) {
 
 extern "C" int rd_wgrad(const RdConvDesc* d, const float* in, const float* dout, float* slabs, void* stream) {
     RD_CHECK_ARG(d && in && dout && slabs, "wgrad: null argument");
+    // (every kernel behind this entry point stages 16-byte words: global_load_lds_dwordx4 / float4)
+    RD_CHECK_ARG(aligned16(in) && aligned16(dout) && aligned16(slabs), "wgrad: unaligned tensor");
     WgradPlan pl;
     WgradArgs a;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -956,10 +959,12 @@ extern "C" int rd_wgrad(const RdConvDesc* d, const float* in, const float* dout,
 extern "C" int rd_wgrad_reduce(const RdConvDesc* d, const float* slabs, float* grad_oihw, int32_t O, int32_t I, int32_t KH,
                                int32_t KW, int32_t co_off, int32_t accumulate, void* stream) {
     RD_CHECK_ARG(d && slabs && grad_oihw, "wgrad_reduce: null argument");
+    RD_CHECK_ARG(aligned16(slabs), "wgrad_reduce: unaligned slabs");
     WgradPlan pl;
     int rc = plan_any(*d, pl);
     if (rc != RD_OK) return rc;
-    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin && co_off + O <= d->Cout, "wgrad_reduce: shape mismatch");
+    RD_CHECK_WGRAD_COLS(*d, O, co_off, "wgrad_reduce");
+    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin, "wgrad_reduce: shape mismatch");
     const int64_t E = (int64_t)pl.S * d->Cin * d->Cout;
     float* tmp = const_cast<float*>(slabs) + (int64_t)pl.slab_splits * E;
     return launch_slab_reduce(slabs, pl.slab_splits, E, tmp, grad_oihw, pl.S, d->Cin, d->Cout, O, I, co_off, accumulate,
@@ -972,6 +977,9 @@ namespace rd { bool wgrad_bf16_reduce_shape(const RdConvDesc* d, int* slab_split
 extern "C" int rd_wgrad_reduce_job(const RdConvDesc* d, int32_t bf16_kernel, const float* slabs, float* grad_oihw, int32_t O, int32_t I,
                                    int32_t KH, int32_t KW, int32_t co_off, int32_t accumulate, RdReduceJob* job) {
     RD_CHECK_ARG(d && slabs && grad_oihw && job, "wgrad_reduce_job: null argument");
+    RD_CHECK_ARG(aligned16(slabs), "wgrad_reduce_job: unaligned slabs");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_reduce_job");
+    RD_CHECK_WGRAD_COLS(*d, O, co_off, "wgrad_reduce_job");
     int slab_splits = 0, S = 0;
     if (bf16_kernel) {
         if (!wgrad_bf16_reduce_shape(d, &slab_splits, &S)) { set_error("wgrad_reduce_job: unsupported descriptor"); return RD_EINVAL; }
@@ -981,7 +989,7 @@ extern "C" int rd_wgrad_reduce_job(const RdConvDesc* d, int32_t bf16_kernel, con
         if (rc != RD_OK) return rc;
         slab_splits = pl.slab_splits; S = pl.S;
     }
-    RD_CHECK_ARG(KH * KW == S && I == d->Cin && co_off + O <= d->Cout, "wgrad_reduce_job: shape mismatch");
+    RD_CHECK_ARG(KH * KW == S && I == d->Cin, "wgrad_reduce_job: shape mismatch");
     return make_reduce_job(slabs, slab_splits, (int64_t)S * d->Cin * d->Cout, grad_oihw, S, d->Cin, d->Cout, O, I, co_off, accumulate, job);
 }
 

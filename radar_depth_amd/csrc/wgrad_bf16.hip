@@ -337,6 +337,7 @@ static bool wgrad_bf16_plan(const RdConvDesc* d, WgradBfPlan& pl) {
     if (!d || d->n_phases < 1 || d->n_phases > RD_MAX_PHASES) return false;
     if (d->in_stride < 1 || d->in_stride > 2 || d->out_stride < 1 || d->out_stride > 2) return false;
     if (d->Cin % 16 != 0 || d->Cout % 16 != 0 || d->ldi % 4 != 0 || d->ldo % 4 != 0) return false;
+    if (!wgrad_strides_ok(*d)) return false;
     if ((int64_t)d->Hi * d->Wi * d->ldi * 4 >= (int64_t)WB_OOB || (int64_t)d->Ho * d->Wo * d->ldo * 4 >= (int64_t)WB_OOB) return false;
     const int IS = d->in_stride;
     pl.lh = d->phase[0].lh; pl.lw = d->phase[0].lw;
@@ -410,6 +411,8 @@ extern "C" int rd_wgrad_bf16_supported(const RdConvDesc* d) {
 }
 
 extern "C" int64_t rd_wgrad_bf16_workspace_floats(const RdConvDesc* d) {
+    if (!d) return RD_EINVAL;
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_bf16");
     WgradBfPlan pl;
     if (!wgrad_bf16_plan(d, pl)) { set_error("wgrad_bf16: unsupported descriptor"); return RD_EINVAL; }
     return (int64_t)(pl.slab_splits + 16) * pl.S * d->Cin * d->Cout;
@@ -426,6 +429,8 @@ extern "C" int rd_wgrad_bf16_plan_info(const RdConvDesc* d, int32_t* out) {
 
 static int wgrad_bf16_impl(bool io16, const RdConvDesc* d, const void* in, const void* dout, float* slabs, void* stream) {
     RD_CHECK_ARG(d && in && dout && slabs, "wgrad_bf16: null argument");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_bf16");
+    RD_CHECK_ARG(aligned16(in) && aligned16(dout) && aligned16(slabs), "wgrad_bf16: unaligned tensor");
     RD_CHECK_ARG(!io16 || (d->ldi % 8 == 0 && d->ldo % 8 == 0), "wgrad_bf16: bf16 storage needs channel strides that are multiples of 8");
     WgradBfPlan pl;
     if (!wgrad_bf16_plan(d, pl)) { set_error("wgrad_bf16: unsupported descriptor"); return RD_EINVAL; }
@@ -484,9 +489,12 @@ extern "C" int rd_wgrad_bf16_t(int32_t dtype, const RdConvDesc* d, const void* i
 extern "C" int rd_wgrad_bf16_reduce(const RdConvDesc* d, const float* slabs, float* grad_oihw, int32_t O, int32_t I, int32_t KH,
                                     int32_t KW, int32_t co_off, int32_t accumulate, void* stream) {
     RD_CHECK_ARG(d && slabs && grad_oihw, "wgrad_bf16_reduce: null argument");
+    RD_CHECK_ARG(aligned16(slabs), "wgrad_bf16_reduce: unaligned slabs");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_bf16_reduce");
     WgradBfPlan pl;
     if (!wgrad_bf16_plan(d, pl)) { set_error("wgrad_bf16_reduce: unsupported descriptor"); return RD_EINVAL; }
-    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin && co_off + O <= d->Cout, "wgrad_bf16_reduce: shape mismatch");
+    RD_CHECK_WGRAD_COLS(*d, O, co_off, "wgrad_bf16_reduce");
+    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin, "wgrad_bf16_reduce: shape mismatch");
     const int64_t E = (int64_t)pl.S * d->Cin * d->Cout;
     float* tmp = const_cast<float*>(slabs) + (int64_t)pl.slab_splits * E;
     return launch_slab_reduce(slabs, pl.slab_splits, E, tmp, grad_oihw, pl.S, d->Cin, d->Cout, O, I, co_off, accumulate,

@@ -389,6 +389,7 @@ static bool ws_shape_ok(const RdConvDesc& d) {
     }
     if (d.n_phases == 1 && d.phase[0].n_taps != 9) return false;
     if (d.Cin < 64 || d.Cout < 64 || d.Cin % 8 != 0 || d.Cout % 8 != 0 || d.ldi % 4 != 0 || d.ldo % 4 != 0) return false;
+    if (!wgrad_strides_ok(d)) return false;
     if ((int64_t)d.Hi * d.Wi * d.ldi * 4 >= (int64_t)WS_OOB || (int64_t)d.Ho * d.Wo * d.ldo * 4 >= (int64_t)WS_OOB) return false;
     return true;
 }
@@ -443,6 +444,7 @@ extern "C" int rd_wgrad_split_supported(const RdConvDesc* d) { return d && ws_sh
 
 extern "C" int64_t rd_wgrad_split_workspace_floats(const RdConvDesc* d) {
     if (!d) return RD_EINVAL;
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_split");
     const WsPlan pl = ws_plan(*d);
     if (!pl.ok) return RD_EINVAL;
     return (int64_t)(pl.n_splits + pl.J) * pl.S * d->Cin * d->Cout;
@@ -496,9 +498,10 @@ static void ws_fill_args(const RdConvDesc* d, const WsPlan& pl, WsArgs& a) {
 
 extern "C" int rd_wgrad_split(const RdConvDesc* d, const float* in, const float* dout, float* slabs, void* stream) {
     RD_CHECK_ARG(d && in && dout && slabs, "wgrad_split: null argument");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_split");
     const WsPlan pl = ws_plan(*d);
     if (!pl.ok) { set_error("wgrad_split: descriptor not supported (rd_wgrad_split_supported)"); return RD_EINVAL; }
-    RD_CHECK_ARG(reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(dout) % 16 == 0, "wgrad_split: unaligned tensor");
+    RD_CHECK_ARG(aligned16(in) && aligned16(dout) && aligned16(slabs), "wgrad_split: unaligned tensor");
     WsArgs a;
     ws_fill_args(d, pl, a);
     a.x = in; a.dy = dout; a.slabs = slabs;
@@ -513,9 +516,10 @@ extern "C" int rd_wgrad_split_pre_supported(const RdConvDesc* d) { return d && w
 extern "C" int rd_wgrad_split_pre(const RdConvDesc* d, const void* x_pieces, int64_t x_piece_elems, const void* dy_pieces, int64_t dy_piece_elems,
                                   float* slabs, void* stream) {
     RD_CHECK_ARG(d && x_pieces && dy_pieces && slabs, "wgrad_split_pre: null argument");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_split_pre");
     const WsPlan pl = ws_plan(*d);
     if (!pl.ok || d->Cin % 16 || d->Cout % 16) { set_error("wgrad_split_pre: descriptor not supported (rd_wgrad_split_pre_supported)"); return RD_EINVAL; }
-    RD_CHECK_ARG(reinterpret_cast<uintptr_t>(x_pieces) % 16 == 0 && reinterpret_cast<uintptr_t>(dy_pieces) % 16 == 0, "wgrad_split_pre: unaligned tensor");
+    RD_CHECK_ARG(aligned16(x_pieces) && aligned16(dy_pieces) && aligned16(slabs), "wgrad_split_pre: unaligned tensor");
     WsArgs a;
     ws_fill_args(d, pl, a);
     RD_CHECK_ARG(x_piece_elems >= (int64_t)d->Cin * a.xm && dy_piece_elems >= (int64_t)d->Cout * a.ym && x_piece_elems % 8 == 0 && dy_piece_elems % 8 == 0,
@@ -529,9 +533,12 @@ extern "C" int rd_wgrad_split_pre(const RdConvDesc* d, const void* x_pieces, int
 extern "C" int rd_wgrad_split_reduce(const RdConvDesc* d, const float* slabs, float* grad_oihw, int32_t O, int32_t I, int32_t KH, int32_t KW,
                                      int32_t co_off, int32_t accumulate, void* stream) {
     RD_CHECK_ARG(d && slabs && grad_oihw, "wgrad_split_reduce: null argument");
+    RD_CHECK_ARG(aligned16(slabs), "wgrad_split_reduce: unaligned slabs");
+    RD_CHECK_WGRAD_STRIDES(*d, "wgrad_split_reduce");
     const WsPlan pl = ws_plan(*d);
     if (!pl.ok) { set_error("wgrad_split_reduce: descriptor not supported"); return RD_EINVAL; }
-    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin && co_off >= 0 && co_off + O <= d->Cout, "wgrad_split_reduce: gradient shape does not match the descriptor");
+    RD_CHECK_WGRAD_COLS(*d, O, co_off, "wgrad_split_reduce");
+    RD_CHECK_ARG(KH * KW == pl.S && I == d->Cin, "wgrad_split_reduce: gradient shape does not match the descriptor");
     const int64_t E = (int64_t)pl.S * d->Cin * d->Cout;
     float* tmp = const_cast<float*>(slabs) + (int64_t)pl.n_splits * E;
     return launch_slab_reduce(slabs, pl.n_splits, E, tmp, grad_oihw, pl.S, d->Cin, d->Cout, O, I, co_off, accumulate, static_cast<hipStream_t>(stream));

@@ -98,12 +98,17 @@ def gemm_taps_split(desc, x, w_split, out, bias=None, act=0, act_cols=0, addend=
 
 
 def split_pieces(x_nhwc):
-    """fp32 NHWC tensor -> three bf16 piece planes [3][C/16][M][16] (rd_split_pieces; x = p0 + p1 + p2 exactly)."""
+    """fp32 NHWC tensor -> three bf16 piece planes [3][C/16][M][16] (rd_split_pieces; x = p0 + p1 + p2 exactly).  x_nhwc may be a
+    channel slice of a wider NHWC buffer (buf[..., c0:c0 + c]): the pixel stride is taken from the tensor."""
     import torch
     n, h, w, c = x_nhwc.shape
     m = n * h * w
+    ld = c if x_nhwc.is_contiguous() else x_nhwc.stride(2)
+    assert x_nhwc.dtype == torch.float32 and x_nhwc.is_cuda and (x_nhwc.is_contiguous() or (
+        x_nhwc.stride(3) == 1 and x_nhwc.stride(1) == w * ld and x_nhwc.stride(0) == h * w * ld)), \
+        "expected an NHWC CUDA float32 tensor (a channel slice of a wider buffer is fine)"
     pc = torch.empty(3, c // 16, m, 16, dtype=torch.bfloat16, device=x_nhwc.device)
-    check(lib().rd_split_pieces(ptr(_f32(x_nhwc)), c, C.c_int64(m), c, ptr(pc), C.c_int64(pc[0].numel()), current_stream()), "rd_split_pieces")
+    check(lib().rd_split_pieces(ptr(x_nhwc), ld, C.c_int64(m), c, ptr(pc), C.c_int64(pc[0].numel()), current_stream()), "rd_split_pieces")
     return pc
 
 
@@ -215,14 +220,18 @@ def wgrad_reduce(desc, slabs, grad_oihw, co_off=0, accumulate=False):
 
 
 def wgrad_reduce_batched(jobs):
-    """jobs: [(desc, slabs, grad_oihw, co_off)] (fp32 rd_wgrad slabs) reduced by ONE rd_wgrad_reduce_batched call (two launches)."""
+    """jobs: [(desc, slabs, grad_oihw, co_off[, bf16_kernel])] reduced by ONE rd_wgrad_reduce_batched call (two launches); bf16_kernel
+    (default 0): the slabs came from rd_wgrad_bf16 rather than rd_wgrad."""
     import numpy as np
     from ._lib import RdReduceJob
     arr = (RdReduceJob * len(jobs))()
     bj1, bj2 = [], []
-    for q, (desc, slabs, grad, co_off) in enumerate(jobs):
+    for q, job in enumerate(jobs):
+        desc, slabs, grad, co_off = job[:4]
+        bf16_kernel = int(job[4]) if len(job) > 4 else 0
         o, i, kh, kw = grad.shape
-        check(lib().rd_wgrad_reduce_job(C.byref(desc), 0, ptr(slabs), ptr(_f32(grad)), o, i, kh, kw, co_off, 0, C.byref(arr[q])), "rd_wgrad_reduce_job")
+        check(lib().rd_wgrad_reduce_job(C.byref(desc), bf16_kernel, ptr(slabs), ptr(_f32(grad)), o, i, kh, kw, co_off, 0, C.byref(arr[q])),
+              "rd_wgrad_reduce_job")
         arr[q].first_block1, arr[q].first_block2 = len(bj1), len(bj2)
         bj1 += [q] * arr[q].n_blocks1
         bj2 += [q] * arr[q].n_blocks2

@@ -357,3 +357,42 @@ def test_bind_input_repoints_the_stem_plane_tables():
     assert list(st_rgb)[:3] == [6 * hw] * 3 and st_d[0] == 6 * hw and plan._x_bound == 1 << 40
     plan.bind_own_input()
     assert pl_rgb[0] == base0 and st_rgb[0] == plan.x_in.shape[1] * hw and plan._x_bound == base0
+
+
+def test_weight_gradient_operands_of_the_plans_against_the_kernel_level_slice_cases(capsys):
+    """Ties tests/test_gpu_wgrad_slices.py to what the plans bind: the (family, descriptor) pairs of every `*.wgrad` entry of the headline
+    split plan and of the bf16-storage plan (b = 16, 450x800), the layers with ldi != Cin or ldo != Cout listed per family, and every
+    (ldi - Cin, ldo - Cout) sign pattern of a family covered by a kernel-level case of that family.
+
+    What the plans bind today: NO weight-gradient launch reads a channel slice.  engine.conv_bwd does take ldi = x.ld and ldo = dout.ld,
+    but every Act that reaches a training convolution is a whole buffer -- the channel slices of the 640-channel concat buffer, of an
+    UpProj module's two halves and of their gradients are read and written by the BatchNorm / activation kernels (bn_act(..., out=
+    cat.chan(...)), bn_join_bwd(..., dx2=dR.chan(...))), which hand the convolutions dense tensors.  The list is therefore pinned EMPTY
+    ("Weight gradients on channel slices"): a plan change that starts binding a slice to a weight-gradient kernel fails here,
+    is listed, and must find its sign pattern among the kernel-level cases -- which cover all four patterns for every family already."""
+    import wgrad_slice_cases as wc
+    from radar_depth_amd.engine import LateFusionPlan
+    m = _model(450, 800)
+    strided = []
+    for label, kw in (("split", dict(split=True)), ("bf16-storage", dict(storage="bf16"))):
+        plan = LateFusionPlan(m, 16, 450, 800, train=True, dry_run=True, **kw)
+        pairs = [(name, fam, d) for name, (fam, d) in plan.meta.items() if name.endswith(".wgrad")]
+        assert len(pairs) == 48, (label, len(pairs))                     # 55 convolutions - 2 stems - conv3 - 4 fused UpProj pairs
+        fams = collections.Counter(fam for _, fam, _ in pairs)
+        assert set(fams) <= set(wc.FAMILY_CASES), fams
+        assert (fams["wgrad_split"] >= 20 and fams["wgrad"] > 0) if label == "split" else fams == {"wgrad_bf16": 48}
+        for name, fam, d in pairs:
+            pattern = (d.ldi > d.Cin, d.ldo > d.Cout)
+            assert d.ldi >= d.Cin and d.ldo >= d.Cout, (label, name)
+            assert pattern in wc.sign_patterns(fam), "%s plan: %s (%s) binds ldi %d / Cin %d, ldo %d / Cout %d: no kernel-level case of that " \
+                "family has this pattern" % (label, name, fam, d.ldi, d.Cin, d.ldo, d.Cout)
+            if any(pattern):
+                strided.append((label, fam, name, d.Cin, d.ldi, d.Cout, d.ldo))
+        with capsys.disabled():
+            print("\n%s plan: %s; weight-gradient launches on channel slices: %s"
+                  % (label, dict(fams), [s for s in strided if s[0] == label] or "none"))
+    # whatever a plan may bind later: all four patterns are exercised at kernel level (rd_wgrad_split_pre reads piece planes, whose
+    # producers take the strides: its kernel never sees ldi / ldo)
+    for fam in ("wgrad", "wgrad_split", "wgrad_bf16"):
+        assert wc.sign_patterns(fam) == {(False, False), (True, False), (False, True), (True, True)}, fam
+    assert strided == [], strided
