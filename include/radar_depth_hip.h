@@ -524,6 +524,45 @@ int rd_uncertainty_total(const double* sums1, const double* sums2, const double*
 /* loss[0] = sums[0]/sums[1]; coef[0] = 1 (plain MaskedL1 step, main.py:440-441) */
 int rd_l1_total(const double* sums, float* loss, float* coef, void* stream);
 
+/* MaskedBerHuLoss (:57-81, `-c berhu`) with the threshold kept on the device: the reference reads max|t-p| back to the host
+ * (`delta = thresh * torch.max(diff).item()`) in the middle of the loss; here delta is formed by the kernels that use it.
+ * Over the valid pixels (target > 0), every step a float32 operation rounded on its own (no contraction):
+ *   diff = |t - p|;  M = max diff;  delta = thresh * (double)M;  thr = (float)(-delta), d2 = (float)(delta*delta), den = (float)(2*delta)
+ *   in1 = (-diff > thr);  y = diff*diff - d2;  in2 = (y > 0)
+ *   term = (in1 ? diff : 0) + ((in2 ? y : -d2) + d2) / den        (a correctly rounded division)
+ * which is the reference's arithmetic, not the textbook's: above the threshold the term is ((diff^2 - d2) + d2) / den, about
+ * diff^2 / (2 delta), and the two comparisons are separate float32 tests, so a pixel at or next to diff = delta can be in neither
+ * branch (term 0, gradient 0) -- the pixel holding the maximum always is when thresh = 1.
+ * rd_masked_berhu_sums: sums[0] = sum of the terms (added in fp64), sums[1] = count, sums[2] = delta, sums[3] = M; sums[0]/sums[1] is
+ * the loss, so rd_l1_total and rd_uncertainty_total take the result as they take rd_masked_l1_sums'.  Three launches (per-block
+ * maxima of the float's bits, which order as integers for non-negative floats and keep a NaN; per-block term sums, every block
+ * forming delta from the maxima; the final sums): no atomics, no host synchronisation, bit-reproducible.
+ * rd_masked_berhu_sums_metrics: the same with the ten sums of rd_depth_metrics riding along in the second pass; sums[4] bit-identical
+ * to the plain call, msums[10] bit-identical to rd_depth_metrics.
+ * rd_masked_berhu_bwd: dpred (+)= -sign(t-p) * k * ([in1] + [in2] * 2 diff / den), k = coef_dev[0] / count, the branches decided
+ * again from sums[2] by the same float32 comparisons; 0 on invalid pixels and where t == p.  The arguments of rd_masked_l1_bwd.
+ * ws: rd_berhu_workspace_floats(n) floats, 8-byte aligned, for either sums call.
+ * All valid pixels equal to the prediction (M == 0): the loss is 0/0 = NaN and the gradient 0, as in the reference.  No valid pixel:
+ * NaN loss and zero gradient too -- the one difference: the reference's torch.max raises there, which needs the readback.
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_EBERHU_NULL    a null pointer
+ *   RD_EBERHU_RANGE   n < 1
+ *   RD_EBERHU_THRESH  thresh not finite or <= 0
+ *   RD_EBERHU_ALIGN   ws, sums or msums not 8-byte aligned
+ * rd_berhu_workspace_floats returns RD_EBERHU_RANGE for an n the calls reject. */
+#define RD_EBERHU_NULL (-34)
+#define RD_EBERHU_RANGE (-35)
+#define RD_EBERHU_THRESH (-36)
+#define RD_EBERHU_ALIGN (-37)
+int64_t rd_berhu_workspace_floats(int64_t n);
+int rd_masked_berhu_sums(const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums,
+                         void* stream);
+int rd_masked_berhu_sums_metrics(const float* pred, const float* target, int64_t n, double thresh, float* ws,
+                                 double* sums, double* msums, void* stream);
+int rd_masked_berhu_bwd(const float* pred, const float* target, int64_t n, const double* sums, const float* coef,
+                        float* dpred, int32_t accumulate, void* stream);
+
 /* torch.optim.SGD step (main.py:285-290,445): g += wd*p; buf = first ? g : mom*buf + g; p -= lr*buf,
  * over a flat arena.  grad_scale multiplies g first (1/world for data-parallel averaging). */
 int rd_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd,

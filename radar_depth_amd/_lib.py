@@ -19,6 +19,8 @@ RD_ESPARSE_NULL, RD_ESPARSE_RANGE, RD_ESPARSE_PIXELS, RD_ESPARSE_STRIDE, RD_ESPA
 RD_ESPARSE_OVERLAP = -26
 # ... and of the comparison-row renderer
 RD_EVIS_NULL, RD_EVIS_RANGE, RD_EVIS_PLANES, RD_EVIS_STRIDE, RD_EVIS_PITCH, RD_EVIS_NAN, RD_EVIS_OVERLAP = -27, -28, -29, -30, -31, -32, -33
+# ... and of the BerHu loss
+RD_EBERHU_NULL, RD_EBERHU_RANGE, RD_EBERHU_THRESH, RD_EBERHU_ALIGN = -34, -35, -36, -37
 
 
 class RdPhase(C.Structure):
@@ -69,13 +71,18 @@ def lib():
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
                      "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats",
-                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes"):
+                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes", "rd_berhu_workspace_floats"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
         # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
         vp = C.c_void_p
         for name, args in (("rd_masked_l1_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
                            ("rd_masked_l2_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
+                           # MaskedBerHuLoss (thresh travels as a double)
+                           ("rd_berhu_workspace_floats", [C.c_int64]),
+                           ("rd_masked_berhu_sums", [vp, vp, C.c_int64, C.c_double, vp, vp, vp]),
+                           ("rd_masked_berhu_sums_metrics", [vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp]),
+                           ("rd_masked_berhu_bwd", [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp]),
                            ("rd_depth_metrics_frames_workspace_floats", [C.c_int32, C.c_int64]),
                            ("rd_depth_metrics_frames", [vp, vp, C.c_int32, C.c_int64, vp, vp, vp]),
                            ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),

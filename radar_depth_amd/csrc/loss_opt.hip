@@ -1,5 +1,5 @@
 // Losses, the multistage radar filter and the optimizer step -- the tail of the reference's training-step body
-// (main.py:416-445): MaskedL1Loss (evaluation/criteria_new.py:44-54), SmoothnessLoss (:8-28), the
+// (main.py:416-445): MaskedL1Loss (evaluation/criteria_new.py:44-54), MaskedBerHuLoss (:57-81), SmoothnessLoss (:8-28), the
 // uncertainty-weighted total (main.py:423-429), Filter_layer (model/multistage_model.py:87-119) and
 // torch.optim.SGD with momentum + weight decay (main.py:285-290,445).  All scalars stay on the device.
 #include "common.h"
@@ -147,6 +147,152 @@ __global__ __launch_bounds__(256) void split_final_kernel(const double* __restri
             if (k < na) out_a[k] = s;
             else out_b[k - na] = s;
         }
+    }
+}
+
+// ---------------------------------------------------------------- masked BerHu (criteria_new.py:57-81)
+// The reference forms delta = thresh * max|t-p| on the host (a blocking .item() in the middle of the loss) and then works in fp32
+// tensors with delta, delta^2 and 2 delta rounded to fp32 where they meet one.  Here the maximum stays on the device: pass 1 leaves one
+// maximum per block, every block of pass 2 reduces those (<= RED_BLOCKS words) and forms the three constants itself.
+// The maximum is taken on the BITS of |t-p|: non-negative floats order as unsigned integers, so it is exact and independent of the
+// order, and a NaN difference (a diverged prediction) is the largest of all and reaches the loss as it does in the reference.
+__device__ __forceinline__ unsigned block_max_u(unsigned v, unsigned* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned w = (unsigned)__shfl_xor((int)v, o, 64);
+        v = w > v ? w : v;
+    }
+    rd_sync();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    rd_sync();
+    unsigned m = 0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) m = sh[i] > m ? sh[i] : m;
+    return m;
+}
+__device__ __forceinline__ unsigned blocks_max_u(const unsigned* __restrict__ pmax, int nblocks, unsigned* sh) {
+    unsigned m = 0;
+    for (int i = threadIdx.x; i < nblocks; i += blockDim.x) m = pmax[i] > m ? pmax[i] : m;
+    return block_max_u(m, sh);
+}
+
+struct BerhuConsts { float thr, d2, den; };
+__device__ __forceinline__ BerhuConsts berhu_consts(double delta) {
+    BerhuConsts k;
+    k.thr = (float)(-delta);
+    k.d2 = (float)(delta * delta);
+    k.den = (float)(2.0 * delta);
+    return k;
+}
+// The two branch decisions of one valid pixel: separate fp32 comparisons (a pixel can fail both), every operation rounded on its own.
+__device__ __forceinline__ float berhu_branches(float diff, const BerhuConsts& k, bool& in1, bool& in2) {
+#pragma clang fp contract(off)
+    const float y = diff * diff - k.d2;
+    in1 = -diff > k.thr;
+    in2 = y > 0.f;
+    return y;
+}
+__device__ __forceinline__ float berhu_term(float diff, const BerhuConsts& k) {
+#pragma clang fp contract(off)
+    bool in1, in2;
+    const float y = berhu_branches(diff, k, in1, in2);
+    const float part1 = in1 ? diff : 0.f;
+    const float part2 = __fdiv_rn((in2 ? y : -k.d2) + k.d2, k.den);
+    return part1 + part2;
+}
+
+__global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                        unsigned* __restrict__ pmax) {
+    __shared__ unsigned shu[4];
+    unsigned m = 0;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const float t = target[e];
+        if (t > 0.f) {
+            const unsigned b = __float_as_uint(fabsf(t - pred[e]));
+            m = b > m ? b : m;
+        }
+    }
+    m = block_max_u(m, shu);
+    if (threadIdx.x == 0) pmax[blockIdx.x] = m;
+}
+
+// part[block][2 (+ 10)]: sum of terms, count (then the ten metric sums: the grid, the per-thread element order and the block sums of
+// metrics_partial_kernel, so they come out bit-identical); the loss sums do not depend on MET
+template <bool MET>
+__global__ __launch_bounds__(256) void berhu_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                            double thresh, const unsigned* __restrict__ pmax, int nblocks,
+                                                            double* __restrict__ part) {
+    __shared__ double sh[4];
+    __shared__ unsigned shu[4];
+    const BerhuConsts k = berhu_consts(thresh * (double)__uint_as_float(blocks_max_u(pmax, nblocks, shu)));
+    double s = 0.0, c = 0.0;
+    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const float t = target[e];
+        if (t > 0.f) {
+            const float o = pred[e];
+            s += (double)berhu_term(fabsf(t - o), k);
+            c += 1.0;
+            if (MET) metric_terms(o, t, acc);
+        }
+    }
+    s = block_sum_d(s, sh);
+    c = block_sum_d(c, sh);
+    double* o = part + (size_t)blockIdx.x * (MET ? 12 : 2);
+    if (threadIdx.x == 0) {
+        o[0] = s;
+        o[1] = c;
+    }
+    if (MET) {
+        for (int i = 0; i < 10; ++i) {
+            const double v = block_sum_d(acc[i], sh);
+            if (threadIdx.x == 0) o[2 + i] = v;
+        }
+    }
+}
+// split_final_kernel's sums over part[block][2 + nb] (nb = 0: no metric sums), then out_a[2] = delta, out_a[3] = the maximum
+__global__ __launch_bounds__(256) void berhu_final_kernel(const double* __restrict__ part, const unsigned* __restrict__ pmax, int nblocks,
+                                                          int nb, double thresh, double* __restrict__ out_a, double* __restrict__ out_b) {
+    __shared__ double sh[4];
+    __shared__ unsigned shu[4];
+    const int stride = 2 + nb;
+    for (int k = 0; k < stride; ++k) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += part[(size_t)i * stride + k];
+        s = block_sum_d(s, sh);
+        if (threadIdx.x == 0) {
+            if (k < 2) out_a[k] = s;
+            else out_b[k - 2] = s;
+        }
+    }
+    const double m = (double)__uint_as_float(blocks_max_u(pmax, nblocks, shu));
+    if (threadIdx.x == 0) {
+        out_a[2] = thresh * m;
+        out_a[3] = m;
+    }
+}
+
+// autograd of the reference's expression in its own fp32 steps: g = coef / count reaches diff through part1 (where in1) and through
+// part2 as (g / den) * (2 diff) (where in2); |.|' is 0 at t == p
+__global__ __launch_bounds__(256) void berhu_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                        const double* __restrict__ sums, const float* __restrict__ coef,
+                                                        float* __restrict__ dpred, int accumulate) {
+#pragma clang fp contract(off)
+    const float k = (float)((double)coef[0] / sums[1]);
+    const BerhuConsts c = berhu_consts(sums[2]);
+    const float kd = __fdiv_rn(k, c.den);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const float t = target[e];
+        float g = 0.f;
+        if (t > 0.f) {
+            const float d = t - pred[e];
+            const float diff = fabsf(d);
+            bool in1, in2;
+            berhu_branches(diff, c, in1, in2);
+            float a = in1 ? k : 0.f;
+            if (in2) a = a + kd * (2.f * diff);
+            g = d > 0.f ? -a : (d < 0.f ? a : 0.f);
+        }
+        dpred[e] = accumulate ? dpred[e] + g : g;
     }
 }
 
@@ -519,6 +665,50 @@ extern "C" int rd_masked_l2_bwd(const float* pred, const float* target, int64_t 
     hipLaunchKernelGGL(l1_bwd_kernel<true>, dim3(ew_grid2(n)), dim3(256), 0, static_cast<hipStream_t>(stream), pred, target, n, sums, coef,
                        dpred, accumulate);
     RD_CHECK_LAUNCH("l2_bwd_kernel");
+    return RD_OK;
+}
+
+// MaskedBerHuLoss.  workspace layout: doubles part[tiles][12] (the plain call uses [tiles][2] of it) | unsigned pmax[tiles] (padded to even)
+extern "C" int64_t rd_berhu_workspace_floats(int64_t n) {
+    if (n < 1) return RD_EBERHU_RANGE;
+    const int64_t g = red_grid(n);
+    return 2 * 12 * g + ((g + 1) & ~(int64_t)1);
+}
+template <bool MET>
+static int berhu_sums(const char* what, const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums,
+                      double* msums, void* stream) {
+    RD_CHECK_CODE(pred && target && ws && sums && (msums || !MET), RD_EBERHU_NULL, "%s: null argument", what);
+    RD_CHECK_CODE(n >= 1, RD_EBERHU_RANGE, "%s: n = %lld, at least one element is needed", what, (long long)n);
+    RD_CHECK_CODE(std::isfinite(thresh) && thresh > 0.0, RD_EBERHU_THRESH, "%s: thresh = %g has to be finite and positive", what, thresh);
+    RD_CHECK_CODE((((uintptr_t)ws | (uintptr_t)sums | (uintptr_t)msums) & 7) == 0, RD_EBERHU_ALIGN,
+                  "%s: the workspace and the sums have to be 8-byte aligned", what);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int g = red_grid(n);
+    double* part = reinterpret_cast<double*>(ws);
+    unsigned* pmax = reinterpret_cast<unsigned*>(part + (size_t)12 * g);
+    hipLaunchKernelGGL(berhu_max_kernel, dim3(g), dim3(256), 0, s, pred, target, n, pmax);
+    RD_CHECK_LAUNCH("berhu_max_kernel");
+    hipLaunchKernelGGL(berhu_partial_kernel<MET>, dim3(g), dim3(256), 0, s, pred, target, n, thresh, pmax, g, part);
+    RD_CHECK_LAUNCH("berhu_partial_kernel");
+    hipLaunchKernelGGL(berhu_final_kernel, dim3(1), dim3(256), 0, s, part, pmax, g, MET ? 10 : 0, thresh, sums, msums);
+    RD_CHECK_LAUNCH("berhu_final_kernel");
+    return RD_OK;
+}
+extern "C" int rd_masked_berhu_sums(const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums, void* stream) {
+    return berhu_sums<false>("masked_berhu_sums", pred, target, n, thresh, ws, sums, nullptr, stream);
+}
+extern "C" int rd_masked_berhu_sums_metrics(const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums,
+                                            double* msums, void* stream) {
+    return berhu_sums<true>("masked_berhu_sums_metrics", pred, target, n, thresh, ws, sums, msums, stream);
+}
+extern "C" int rd_masked_berhu_bwd(const float* pred, const float* target, int64_t n, const double* sums, const float* coef, float* dpred,
+                                   int32_t accumulate, void* stream) {
+    RD_CHECK_CODE(pred && target && sums && coef && dpred, RD_EBERHU_NULL, "masked_berhu_bwd: null argument");
+    RD_CHECK_CODE(n >= 1, RD_EBERHU_RANGE, "masked_berhu_bwd: n = %lld, at least one element is needed", (long long)n);
+    RD_CHECK_CODE(((uintptr_t)sums & 7) == 0, RD_EBERHU_ALIGN, "masked_berhu_bwd: the sums have to be 8-byte aligned");
+    hipLaunchKernelGGL(berhu_bwd_kernel, dim3(ew_grid2(n)), dim3(256), 0, static_cast<hipStream_t>(stream), pred, target, n, sums, coef,
+                       dpred, accumulate);
+    RD_CHECK_LAUNCH("berhu_bwd_kernel");
     return RD_OK;
 }
 

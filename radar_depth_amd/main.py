@@ -16,6 +16,7 @@ import torch.nn as nn
 from ._lib import check, lib, ptr
 from .model.models import ResNet, ResNet_latefusion
 
+CRITERIA = ("l1", "l2", "berhu")
 HOT_PATH_ARCHS = ("resnet18", "resnet34", "resnet18_latefusion", "resnet18_multistage", "resnet18_multistage_uncertainty_fixs")
 
 
@@ -46,6 +47,24 @@ def create_model(args, output_size):
         raise ValueError("[Error] Unknown model!!")
     print("[Info] model created.")
     return model
+
+
+def create_criterion(args, berhu_thresh=0.2):
+    """main.py:293-305: {"depth": the masked loss `-c` names} plus {"smooth": SmoothnessLoss} for the uncertainty archs; `berhu`
+    (MaskedBerHuLoss) next to the reference's `l1` and `l2`, the reference's ValueError for anything else."""
+    from .evaluation.criteria_new import MaskedBerHuLoss, MaskedL1Loss, MaskedMSELoss, SmoothnessLoss
+    criterion = {}
+    if args.criterion == 'l2':
+        criterion["depth"] = MaskedMSELoss()
+    elif args.criterion == 'l1':
+        criterion["depth"] = MaskedL1Loss()
+    elif args.criterion == 'berhu':
+        criterion["depth"] = MaskedBerHuLoss(berhu_thresh)
+    else:
+        raise ValueError("[Error] Unknown criterion...")
+    if args.arch in ("resnet18_multistage_uncertainty", "resnet18_multistage_uncertainty_fixs"):
+        criterion["smooth"] = SmoothnessLoss()
+    return criterion
 
 
 def _param_offsets(root):
@@ -134,8 +153,11 @@ class HipTrainStep:
     fp32 tolerances unchanged; everything else is the fp32 path."""
 
     def __init__(self, model, batch, height, width, lr=0.01, momentum=0.9, weight_decay=1e-4, loss_weights=None, use_graph=False,
-                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None, metrics=False):
-        """criterion: "l1" (MaskedL1Loss, the default of utils.parse_command) or "l2" (MaskedMSELoss, `-c l2`, main.py:294-305).
+                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None, metrics=False, berhu_thresh=0.2):
+        """criterion: "l1" (MaskedL1Loss, the default of utils.parse_command), "l2" (MaskedMSELoss, `-c l2`, main.py:294-305) or "berhu"
+        (MaskedBerHuLoss(berhu_thresh), `-c berhu`; its threshold thresh * max|target - pred| is formed on the device, so the step stays
+        free of host synchronisation and capturable); on the multistage archs both stage losses are of the chosen kind.  Anything else
+        raises the reference's ValueError.
         comm: "rccl" = the C ABI's own communicator (radar_depth_amd.comm, rd_allreduce_bucket on a dedicated communication
         stream, event-chained behind each backward segment); "torch" = torch.distributed.all_reduce (the cross-check);
         "auto" = rccl when radar_depth_amd.comm is initialised, else torch when torch.distributed is, else single-GPU.
@@ -144,7 +166,8 @@ class HipTrainStep:
         (evaluation.metrics.DeviceAverageMeter; self.meter_stage1 for the multistage archs, per rank when data-parallel).  Nothing
         is read back until meter.average() / meter.last() is called."""
         from .model.multistage_model import ResNet_multistage
-        assert criterion in ("l1", "l2"), criterion
+        if criterion not in CRITERIA:
+            raise ValueError("[Error] Unknown criterion...")
         # storage="bf16": NHWC activations and their gradients live in HBM as bf16 (implies bf16 conv operands); BatchNorm
         # statistics, losses, parameters, their gradients and the optimizer stay fp32 -- BASELINE.json configs 3 / 5
         assert storage in ("fp32", "bf16"), storage
@@ -164,8 +187,10 @@ class HipTrainStep:
         native = comm == "rccl" or (comm == "auto" and (_comm0.initialised() or not tdist0))
         joins = bool(use_graph) or not native
         self.L = lib()
-        self._f_sums, self._f_bwd = ((self.L.rd_masked_l1_sums, self.L.rd_masked_l1_bwd) if criterion == "l1" else
-                                     (self.L.rd_masked_l2_sums, self.L.rd_masked_l2_bwd))
+        self.criterion = criterion
+        self._f_sums, self._f_bwd, self._f_sums_metrics = [getattr(self.L, "rd_masked_%s_%s" % (criterion, k)) for k in ("sums", "bwd", "sums_metrics")]
+        # what the sums calls take between n and the workspace: BerHu's thresh
+        self._sums_extra = (C.c_double(float(berhu_thresh)),) if criterion == "berhu" else ()
         model.train()
         self.multistage = isinstance(model, ResNet_multistage)
         if self.multistage:
@@ -205,8 +230,13 @@ class HipTrainStep:
         self.target = torch.zeros(batch, 1, p.Ho, p.Wo, device=dev)
         tiles = self.L.rd_loss_tiles(C.c_int64(self.n_out))
         self.l1_ws = torch.zeros(2 * tiles, dtype=torch.float64, device=dev)
-        self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
-        self.sums2 = torch.zeros(2, dtype=torch.float64, device=dev)
+        if criterion == "berhu":                              # one workspace serves the plain call and the one with the metric sums
+            nfl = int(self.L.rd_berhu_workspace_floats(self.n_out))
+            check(min(nfl, 0), "rd_berhu_workspace_floats")
+            self.l1_ws = torch.zeros((nfl + 1) // 2, dtype=torch.float64, device=dev)
+        # sum, count of the loss (BerHu: also delta and max |target - pred|, which never leave the device)
+        self.sums = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.sums2 = torch.zeros(4, dtype=torch.float64, device=dev)
         self.loss = torch.zeros(1, device=dev)
         self.coef = torch.zeros(1, device=dev)
         if self.multistage:
@@ -228,8 +258,7 @@ class HipTrainStep:
         self.meter, self.meter_stage1 = None, None
         if self.metrics:
             from .evaluation.metrics import DeviceAverageMeter
-            self._f_sums_metrics = self.L.rd_masked_l1_sums_metrics if criterion == "l1" else self.L.rd_masked_l2_sums_metrics
-            self.metrics_ws = torch.zeros(12 * tiles, dtype=torch.float64, device=dev)
+            self.metrics_ws = self.l1_ws if criterion == "berhu" else torch.zeros(12 * tiles, dtype=torch.float64, device=dev)
             self.meter = DeviceAverageMeter(device=dev)
             self.meter_stage1 = DeviceAverageMeter(device=dev) if self.multistage else None
             # per prediction tensor: (ten metric sums of the step, its meter); the meters' weight is the batch size (main.py:452)
@@ -340,11 +369,12 @@ class HipTrainStep:
     def _l1_ops(self, tag, pred, sums, s):
         if self.metrics:
             msums, meter = self._meter_of[id(pred)]
-            return [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(self.metrics_ws),
-                                                                   ptr(sums), ptr(msums), s)),
+            return [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
+                     (ptr(self.metrics_ws), ptr(sums), ptr(msums), s)),
                     (tag + ".meter", self.L.rd_meter_update, (ptr(msums), 1, ptr(self._meter_weight), None, 1, ptr(meter.buf),
                                                               ptr(meter.last_buf), s))]
-        return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(self.l1_ws), ptr(sums), s))]
+        return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
+                 (ptr(self.l1_ws), ptr(sums), s))]
 
     def _l1_bwd_ops(self, tag, pred, sums, coef, dpred, accumulate, s):
         return [(tag + ".bwd", self._f_bwd, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(sums), coef, ptr(dpred), accumulate, s))]

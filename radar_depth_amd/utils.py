@@ -26,7 +26,7 @@ MODEL_NAMES = ['resnet18', 'resnet34', 'resnet50', 'resnet18_new', 'resnet18_lat
 
 
 def parse_command(argv=None):
-    loss_names = ['l1', 'l2']
+    loss_names = ['l1', 'l2', 'berhu']                 # berhu: evaluation/criteria_new.py:57-81, the one masked criterion main.py never offered
     data_names = ['nuscenes']
     sparsifier_names = ["uniform", "lidar_radar", "radar", "radar_filtered", "radar_filtered2"]
     modality_names = ['rgb', 'rgbd', 'd']
