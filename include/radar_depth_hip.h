@@ -504,6 +504,44 @@ int rd_depth_metrics_frames(const float* output, const float* target, int32_t fr
  * rmse, mae, absrel, lg10, delta1, delta2, delta3), number of updates.  last[10] = the metrics of row rows-1. */
 int rd_meter_update(const double* sums, int32_t rows, const double* weights, const int32_t* groups,
                     int32_t n_groups, double* meter, double* last, void* stream);
+
+/* Result_multidist.evaluate (evaluation/metrics.py:90-138) in one read of output and target (csrc/metrics_multidist.hip).
+ * Interval k of n_intervals (1..16) is [lo_k, hi_k], both ends closed: lo_0 = 0, lo_k = edges[k-1], hi_k = edges[k], and the LAST
+ * upper bound is +inf (edges[n_intervals-1] is never a bound, as in the reference).  A pixel is in interval k when
+ * target > 0 && target >= lo_k && target <= hi_k (float32 comparisons), so a target exactly on an inner edge is in two intervals.
+ * edges: HOST array of n_intervals floats, copied into the kernel arguments; NULL = the reference's 10, 20, ..., 100 (n_intervals
+ * must then be 10).  sums[frames][n_intervals][10] in rd_depth_metrics' order: the ten float32 terms of a pixel are evaluated once
+ * and added in float64 into every interval the pixel is in; a frame/interval without a pixel gets a row of zeros.
+ * frames = 1, hw = numel is the whole-tensor form.  Two launches, no memset, no atomics, no host synchronisation; the summation
+ * order is fixed by the geometry, so two runs give the same bits.
+ * ws: rd_depth_metrics_multidist_workspace_floats(frames, hw, n_intervals) floats, 8-byte aligned (a negative code for arguments
+ * the call rejects).
+ *
+ * rd_meter_update_multidist: rd_meter_update per interval, one launch.  Row r / interval k of sums[rows][n_intervals][10] with
+ * count c > 0 becomes the ten metrics exactly as rd_meter_update forms them and is added, weighted by weights[r] (NULL = 1), into
+ * meter[g][k][12] for every group bit set in groups[r] (NULL = bit 0); c == 0 adds nothing (neither sum, count nor update
+ * counter): AverageMeter_multidist.update skips an interval whose valid_label is 0.  last[n_intervals][10] = the metrics of row
+ * rows-1 (NaN where it is empty), valid[n_intervals] (int32) = 1 / 0 for that row.
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_EMDIST_NULL    a null pointer
+ *   RD_EMDIST_RANGE   frames < 1, hw < 1, rows < 1, n_intervals outside 1..16 (or not 10 with edges == NULL), n_groups outside 1..31
+ *   RD_EMDIST_ALIGN   ws, sums (or meter, last) not 8-byte aligned
+ *   RD_EMDIST_EDGES   edges not finite, not positive or not strictly increasing
+ *   RD_EMDIST_FRAMES  frames > 65535 (one grid row per frame) */
+#define RD_EMDIST_NULL (-38)
+#define RD_EMDIST_RANGE (-39)
+#define RD_EMDIST_ALIGN (-40)
+#define RD_EMDIST_EDGES (-41)
+#define RD_EMDIST_FRAMES (-42)
+#define RD_MDIST_MAX_INTERVALS 16
+int64_t rd_depth_metrics_multidist_workspace_floats(int32_t frames, int64_t hw, int32_t n_intervals);
+int rd_depth_metrics_multidist(const float* output, const float* target, int32_t frames, int64_t hw, const float* edges,
+                               int32_t n_intervals, float* ws, double* sums, void* stream);
+int rd_meter_update_multidist(const double* sums, int32_t rows, int32_t n_intervals, const double* weights,
+                              const int32_t* groups, int32_t n_groups, double* meter, double* last, int32_t* valid,
+                              void* stream);
+
 /* SmoothnessLoss (:8-28) on pred [N,1,H,W] and image [N,C,H,W] (NCHW).  out[0] = loss.
  * ws: rd_smooth_workspace_floats(N,H,W) floats, 8-byte aligned; rd_smooth_bwd reuses what fwd left there. */
 int64_t rd_smooth_workspace_floats(int32_t N, int32_t H, int32_t W);

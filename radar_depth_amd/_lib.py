@@ -21,6 +21,9 @@ RD_ESPARSE_OVERLAP = -26
 RD_EVIS_NULL, RD_EVIS_RANGE, RD_EVIS_PLANES, RD_EVIS_STRIDE, RD_EVIS_PITCH, RD_EVIS_NAN, RD_EVIS_OVERLAP = -27, -28, -29, -30, -31, -32, -33
 # ... and of the BerHu loss
 RD_EBERHU_NULL, RD_EBERHU_RANGE, RD_EBERHU_THRESH, RD_EBERHU_ALIGN = -34, -35, -36, -37
+# ... and of the distance-interval metrics
+RD_EMDIST_NULL, RD_EMDIST_RANGE, RD_EMDIST_ALIGN, RD_EMDIST_EDGES, RD_EMDIST_FRAMES = -38, -39, -40, -41, -42
+RD_MDIST_MAX_INTERVALS = 16
 
 
 class RdPhase(C.Structure):
@@ -71,7 +74,8 @@ def lib():
         for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
                      "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
                      "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats",
-                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes", "rd_berhu_workspace_floats"):
+                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes", "rd_berhu_workspace_floats",
+                     "rd_depth_metrics_multidist_workspace_floats"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
         # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
@@ -86,6 +90,10 @@ def lib():
                            ("rd_depth_metrics_frames_workspace_floats", [C.c_int32, C.c_int64]),
                            ("rd_depth_metrics_frames", [vp, vp, C.c_int32, C.c_int64, vp, vp, vp]),
                            ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
+                           # the distance-interval metrics (csrc/metrics_multidist.hip)
+                           ("rd_depth_metrics_multidist_workspace_floats", [C.c_int32, C.c_int64, C.c_int32]),
+                           ("rd_depth_metrics_multidist", [vp, vp, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]),
+                           ("rd_meter_update_multidist", [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]),
                            # the radar_filtered sparsifier (csrc/radar_filter.hip)
                            ("rd_radar_filter_points", [vp] * 6 + [C.c_int32] * 3 + [vp] * 5),
                            ("rd_radar_index_map", [vp, vp] + [C.c_int32] * 4 + [vp, vp]),

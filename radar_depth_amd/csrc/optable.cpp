@@ -74,6 +74,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         RD_ENTRY(rd_head_conv_fwd_t), RD_ENTRY(rd_head_conv_bwd_t), RD_ENTRY(rd_head_conv_dgrad_t), RD_ENTRY(rd_head_conv_wgrad_t), RD_ENTRY(rd_bilinear_fwd), RD_ENTRY(rd_bilinear_bwd),
         RD_ENTRY(rd_masked_l1_sums), RD_ENTRY(rd_masked_l1_bwd), RD_ENTRY(rd_masked_l2_sums), RD_ENTRY(rd_masked_l2_bwd),
         RD_ENTRY(rd_masked_l1_sums_metrics), RD_ENTRY(rd_masked_l2_sums_metrics), RD_ENTRY(rd_meter_update),
+        RD_ENTRY(rd_depth_metrics_multidist), RD_ENTRY(rd_meter_update_multidist),
         RD_ENTRY(rd_masked_berhu_sums), RD_ENTRY(rd_masked_berhu_sums_metrics), RD_ENTRY(rd_masked_berhu_bwd),
         RD_ENTRY(rd_l1_total), RD_ENTRY(rd_smooth_fwd), RD_ENTRY(rd_smooth_bwd), RD_ENTRY(rd_uncertainty_total),
         RD_ENTRY(rd_radar_filter), RD_ENTRY(rd_sgd_step),

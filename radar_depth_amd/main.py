@@ -164,7 +164,10 @@ class HipTrainStep:
         metrics: keep the reference's per-step Result / AverageMeter bookkeeping (main.py:449-458) on the device: the loss pass also
         produces the ten metric sums of the prediction and one small launch adds them, weighted by the batch size, into self.meter
         (evaluation.metrics.DeviceAverageMeter; self.meter_stage1 for the multistage archs, per rank when data-parallel).  Nothing
-        is read back until meter.average() / meter.last() is called."""
+        is read back until meter.average() / meter.last() is called.
+        metrics="multidist": all of that, plus the same bookkeeping per distance interval (Result_multidist / AverageMeter_multidist,
+        evaluation/metrics.py:61-176): one binning pass over the prediction and one update behind the loss pass, into
+        self.meter_multidist (DeviceAverageMeter_multidist; self.meter_multidist_stage1 for the multistage archs, per rank too)."""
         from .model.multistage_model import ResNet_multistage
         if criterion not in CRITERIA:
             raise ValueError("[Error] Unknown criterion...")
@@ -265,6 +268,14 @@ class HipTrainStep:
             self._meter_of = {id(pl.pred): (torch.zeros(10, dtype=torch.float64, device=dev), m)
                               for pl, m in zip(self.plans[::-1], (self.meter, self.meter_stage1))}
             self._meter_weight = torch.full((1,), float(batch), dtype=torch.float64, device=dev)
+        if metrics not in (False, True, "multidist"):
+            raise ValueError("HipTrainStep: metrics is False, True or 'multidist', got %r" % (metrics,))
+        self.meter_multidist, self.meter_multidist_stage1 = None, None
+        if metrics == "multidist":
+            from .evaluation.metrics import DeviceAverageMeter_multidist
+            self.meter_multidist = DeviceAverageMeter_multidist(device=dev)
+            self.meter_multidist_stage1 = DeviceAverageMeter_multidist(device=dev) if self.multistage else None
+            self._multidist_of = {id(pl.pred): m for pl, m in zip(self.plans[::-1], (self.meter_multidist, self.meter_multidist_stage1))}
         self.use_graph = use_graph
         self.graphs = None
         self.steps = 0                 # optimizer steps (state_dict: a momentum state exists once > 0)
@@ -369,10 +380,13 @@ class HipTrainStep:
     def _l1_ops(self, tag, pred, sums, s):
         if self.metrics:
             msums, meter = self._meter_of[id(pred)]
-            return [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
-                     (ptr(self.metrics_ws), ptr(sums), ptr(msums), s)),
-                    (tag + ".meter", self.L.rd_meter_update, (ptr(msums), 1, ptr(self._meter_weight), None, 1, ptr(meter.buf),
-                                                              ptr(meter.last_buf), s))]
+            ops = [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
+                    (ptr(self.metrics_ws), ptr(sums), ptr(msums), s)),
+                   (tag + ".meter", self.L.rd_meter_update, (ptr(msums), 1, ptr(self._meter_weight), None, 1, ptr(meter.buf),
+                                                             ptr(meter.last_buf), s))]
+            if self.meter_multidist is not None:        # the same Result per distance interval: one binning pass, one update
+                ops += self._multidist_of[id(pred)].update_ops(tag, pred, self.target, 1, self.n_out, self._meter_weight, None, s)
+            return ops
         return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
                  (ptr(self.l1_ws), ptr(sums), s))]
 
