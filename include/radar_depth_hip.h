@@ -923,6 +923,33 @@ int rd_head_conv_dgrad_t(int32_t dtype, const float* w_oihw, const float* dd, in
 int rd_head_conv_wgrad_t(int32_t dtype, const void* x, int32_t ldx, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C,
                          float* dw_oihw, float* ws, void* stream);
 
+/* PnP-Depth refinement (the reference's pnp_forward_front / pnp_forward_rear halves, model/models.py:380-400,669-707): the two
+ * streaming kernels of the rear half's eval-mode backward (csrc/pnp.hip); the rest of it is the input-gradient forms above on the
+ * folded weights, rd_bilinear_bwd and rd_head_conv_dgrad_t.
+ *   rd_act_gate_t  out = dy where y > 0, 0 elsewhere (a select, as torch's ReLU backward: an inf or NaN of dy behind a closed gate gives 0),
+ *                  on channel slices [M rows][C] of NHWC tensors with channel strides lddy, ldy, ldo.  y is the activation OUTPUT the
+ *                  eval forward keeps.  out == dy with ldo == lddy is the in-place form.  fp32 tensors (dtype = RD_DTYPE_F32), ReLU only.
+ *   rd_pnp_update  z = z - alpha_dev[0] * sign(g), sign as torch.sign (+-0 -> 0, NaN -> NaN, denormals count), ONE fp32 rounding.
+ *                  alpha is read on the device: it may change between replays of a captured graph.
+ * 16-byte accesses where C, the channel strides and the base pointers are multiples of 4 elements / 16 bytes, one element per thread
+ * otherwise.  Refused before anything reaches the GPU, each with its own code:
+ *   RD_EPNP_NULL     a null pointer
+ *   RD_EPNP_RANGE    M <= 0 or C <= 0
+ *   RD_EPNP_STRIDE   a channel stride below C
+ *   RD_EPNP_ACT      an activation other than RD_ACT_RELU
+ *   RD_EPNP_DTYPE    a dtype other than RD_DTYPE_F32
+ *   RD_EPNP_OVERLAP  out shares an element with y, or with dy without being dy; z shares an element with g (slices of one tensor --
+ *                    equal strides -- are judged by their column windows, everything else by its whole extent) */
+#define RD_EPNP_NULL (-43)
+#define RD_EPNP_RANGE (-44)
+#define RD_EPNP_STRIDE (-45)
+#define RD_EPNP_ACT (-46)
+#define RD_EPNP_DTYPE (-47)
+#define RD_EPNP_OVERLAP (-48)
+int rd_act_gate_t(int32_t dtype, const void* dy, int32_t lddy, const void* y, int32_t ldy, void* out, int32_t ldo, int64_t M, int32_t C,
+                  int32_t act, void* stream);
+int rd_pnp_update(float* z, int32_t ldz, const float* g, int32_t ldg, int64_t M, int32_t C, const float* alpha_dev, void* stream);
+
 /* Plan tuner for rd_gconv / rd_gconv_ws (the role cudnn.benchmark plays for the reference's convolutions): list the candidate
  * execution plans of a descriptor (9 ints each: MT, NT, WM, WN, CKP, TH, TW, ksplit, loop form -- 0 plain, 1 software-pipelined,
  * 2 pipelined with half-depth weight slabs (more resident workgroups, more barriers); best heuristic score first; returns

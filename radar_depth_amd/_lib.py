@@ -24,6 +24,8 @@ RD_EBERHU_NULL, RD_EBERHU_RANGE, RD_EBERHU_THRESH, RD_EBERHU_ALIGN = -34, -35, -
 # ... and of the distance-interval metrics
 RD_EMDIST_NULL, RD_EMDIST_RANGE, RD_EMDIST_ALIGN, RD_EMDIST_EDGES, RD_EMDIST_FRAMES = -38, -39, -40, -41, -42
 RD_MDIST_MAX_INTERVALS = 16
+# ... and of the PnP-Depth kernels (csrc/pnp.hip)
+RD_EPNP_NULL, RD_EPNP_RANGE, RD_EPNP_STRIDE, RD_EPNP_ACT, RD_EPNP_DTYPE, RD_EPNP_OVERLAP = -43, -44, -45, -46, -47, -48
 
 
 class RdPhase(C.Structure):
@@ -94,6 +96,9 @@ def lib():
                            ("rd_depth_metrics_multidist_workspace_floats", [C.c_int32, C.c_int64, C.c_int32]),
                            ("rd_depth_metrics_multidist", [vp, vp, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]),
                            ("rd_meter_update_multidist", [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]),
+                           # the PnP-Depth kernels (csrc/pnp.hip)
+                           ("rd_act_gate_t", [C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, vp]),
+                           ("rd_pnp_update", [vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp]),
                            # the radar_filtered sparsifier (csrc/radar_filter.hip)
                            ("rd_radar_filter_points", [vp] * 6 + [C.c_int32] * 3 + [vp] * 5),
                            ("rd_radar_index_map", [vp, vp] + [C.c_int32] * 4 + [vp, vp]),

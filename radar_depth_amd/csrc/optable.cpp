@@ -82,6 +82,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         RD_ENTRY(rd_debug_poison_lds),
         RD_ENTRY(rd_gconv_split_pre), RD_ENTRY(rd_wgrad_split_pre), RD_ENTRY(rd_split_pieces),
         RD_ENTRY(rd_wino_conv3x3), RD_ENTRY(rd_wino_pack_batched), RD_ENTRY(rd_wino_conv3x3_bnbwd), RD_ENTRY(rd_gconv_split_bnbwd), RD_ENTRY(rd_gconv_split_pre_bnbwd),
+        RD_ENTRY(rd_act_gate_t), RD_ENTRY(rd_pnp_update),
         RD_ENTRY(rd_bn_act_p), RD_ENTRY(rd_bn_bwd_apply_p), RD_ENTRY(rd_bn_bwd_apply_x_p), RD_ENTRY(rd_bn_bwd_apply_x2_p), RD_ENTRY(rd_bnact_maxpool_fwd_p),
     };
     return r;

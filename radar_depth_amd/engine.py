@@ -108,14 +108,25 @@ CONV_KINDS = ("conv", "upproj", "deconv")
 
 class LateFusionPlan:
     def __init__(self, module, batch, height, width, train=True, depth_planes=None, x_source=None, dense_grad_dst=None,
-                 dry_run=False, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False):
+                 dry_run=False, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False, pnp=False):
         """module: a radar_depth_amd ResNet_latefusion(2); bf16: run the gconv-lowered convolutions with bf16 operands on
         v_mfma_f32_32x32x16_bf16 (fp32 tensors, fp32 accumulation -- BASELINE.json configs 3/5, opt-in; in train plans the
         forward and input-gradient convolutions and the weight gradients of the >= 32-channel layers -- wgrad_bf16.hip; the
         16-channel layers, stems and head keep their fp32 weight-gradient kernels); depth_planes: None (depth stem reads channel(s) 3.. of the
         network input) or, for stage 2 of the multistage net, a list of stand-alone [N,H,W] maps; x_source: share another
         plan's static input buffer (stage 2 reads the RGB planes of stage 1's); dense_grad_dst: [N,H,W]-sized buffer that
-        receives the gradient w.r.t. the second depth plane (stage-1 prediction, multistage_model.py:75)."""
+        receives the gradient w.r.t. the second depth plane (stage-1 prediction, multistage_model.py:75); pnp: an eval plan that
+        also carries the input gradient of its rear half (decoder, conv3, bilinear resize) w.r.t. the bn2 output, for PnP-Depth
+        refinement (_build_pnp_backward)."""
+        # pnp: PnP-Depth refinement (the reference's pnp_forward_front / pnp_forward_rear, models.py:669-707): fp32 eval plans only
+        self.pnp = bool(pnp)
+        if self.pnp and train:
+            raise ValueError("pnp=True is an eval-mode plan (train=False): the halves of PnP-Depth run on running statistics")
+        if self.pnp and (bf16 or storage == "bf16"):
+            raise NotImplementedError("PnP-Depth plans serve fp32 operands and fp32 storage: bf16 operands / bf16 storage are outside their scope")
+        self.pnp_bwd = []      # the rear half's input gradient (pnp plans): dpred -> pnp_g, on the main stream only
+        self._pnp_rear = False   # True while the rear half's folded convolutions are being built (conv_bn_eval keeps their contexts)
+        self._pnp_convs = {}
         self.m = module
         self.N, self.H, self.W = batch, height, width
         self.train = train
@@ -755,7 +766,27 @@ class LateFusionPlan:
         self.keep += [d, scale]
         self._launch_conv(self.fwd, name, "gconv_bf16" if self.bf16 else "gconv", d, x, wp, out, k, addend=addend,
                           epilogue=(_p(bias), act, cout if act_cols is None else act_cols))
+        if self._pnp_rear:
+            self._pnp_convs[name] = self._pnp_operand(name, x, out, d, parts, k, stride, pad, kind, scale)
         return out
+
+    def _pnp_operand(self, name, x, out, d, parts, k, stride, pad, kind, scale):
+        """Second packed operand of a folded eval convolution of a pnp plan's rear half, for its input gradient: the gradient of
+        conv + BatchNorm in eval mode is the input gradient of the convolution with the FOLDED weights -- the BatchNorm scale
+        multiplies the output channel, which is the reduction index here.  Same pack jobs as a training convolution's (conv_fwd)
+        plus the fold's scale slice, indexed by the source's output channel.  Returns the context _pnp_dgrad launches from."""
+        cin, cout = x.C, out.C
+        weights = [(w, off) for w, off, _ in parts]
+        fam_d = self._conv_families(kind, x, out, d, k, stride, pad, weights)[1]
+        wd, quad_d = self._operand(fam_d, weights[0][0], k * k, cout, cin, 1)
+        for w, off in weights:
+            o, i, kh, kw = w.shape
+            if kind == "deconv":
+                # (the adjoint conv's forward: the plain operand [slab][cout][cin]; the output channels run along dim 1 of the weight)
+                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, 0, i, 0, _ColScale(scale[:i]), quad_d))
+            else:
+                self.pack_jobs.append((w, wd, o, i, kh * kw, cin, off, cout, 1, scale[off:off + o], quad_d))
+        return dict(name=name, x=x, out=out, wd=wd, k=k, stride=stride, pad=pad, kind=kind, cout=cout, dgrad=fam_d)
 
     # ------------------------------------------------------------------ batch norm
     def bn_coeffs(self, name, bn, stat, tiles, ld, c0, count, lst=None):
@@ -1006,7 +1037,8 @@ class LateFusionPlan:
             y = self.conv_bn_eval(name + ".upper_branch.conv2", R.chan(0, half), [(ub.conv2.weight, 0, ub.batchnorm2)], 3, 1, 1, ACT_RELU,
                                   addend=R.chan(half, half))
             self.taps[name] = y
-            return y, None
+            pc = self._pnp_convs
+            return y, dict(name=name, y=y, R=R, half=half, cR=pc[name + ".conv5x5"], c2=pc[name + ".upper_branch.conv2"]) if self._pnp_rear else None
         R, cR = self.conv_fwd(name + ".conv5x5", x, [(ub.conv1.weight, 0), (bb.conv.weight, half)], 5, 1, 2, kind="upproj")
         M = R.M
         co_u1 = self.bn_coeffs(name + ".upper_branch.batchnorm1", ub.batchnorm1, cR["stat"], cR["tiles"], Cc, 0, M)
@@ -1048,7 +1080,7 @@ class LateFusionPlan:
         if not self.train:
             y = self.conv_bn_eval(cname, x, [(conv.weight, 0, bn)], k, 2, cd.deconv_pad(k), ACT_RELU, kind="deconv")
             self.taps[name] = y
-            return y, None
+            return y, dict(name=name, y=y, c=self._pnp_convs[cname]) if self._pnp_rear else None
         r, c = self.conv_fwd(cname, x, [(conv.weight, 0)], k, 2, cd.deconv_pad(k), kind="deconv")
         co = self.bn_coeffs(name + ".batchnorm", bn, c["stat"], c["tiles"], r.C, 0, r.M)
         y = self.bn_act(name, r, co, ACT_RELU)
@@ -1061,7 +1093,7 @@ class LateFusionPlan:
         if not self.train:
             y = self.conv_bn_eval(name + ".conv", x, [(conv.weight, 0, bn)], 5, 1, 2, ACT_RELU, kind="upproj")
             self.taps[name] = y
-            return y, None
+            return y, dict(name=name, y=y, c=self._pnp_convs[name + ".conv"]) if self._pnp_rear else None
         r, c = self.conv_fwd(name + ".conv", x, [(conv.weight, 0)], 5, 1, 2, kind="upproj")
         co = self.bn_coeffs(name + ".batchnorm", bn, c["stat"], c["tiles"], r.C, 0, r.M)
         y = self.bn_act(name, r, co, ACT_RELU)
@@ -1182,14 +1214,78 @@ class LateFusionPlan:
             z = self.bn_act("bn2", self.r2, self.co_c2, ACT_NONE)
         else:
             z = self.taps["bn2"] = self.conv_bn_eval("conv2", x, [(m.conv2.weight, 0, m.bn2)], 1, 1, 0, ACT_NONE)
+        if self.pnp:
+            # the split point of PnP-Depth: the front half ends with bn2 (the latent z), the rear half is fwd[rear_begin:]
+            self.pnp_z, self.rear_begin, self._pnp_rear = z, len(self.fwd), True
         ups = []
         for i in (1, 2, 3, 4):
             z, ctx = dec_fwd("decoder.layer%d" % i, getattr(m.decoder, "layer%d" % i), z)
             ups.append(ctx)
+        self._pnp_rear = False
         if self.train:
             self.ups = ups
         self._head(z)
+        if self.pnp:
+            self._build_pnp_backward(ups)
         self._finish_pack_jobs()
+
+    # ------------------------------------------------------------------ PnP-Depth: input gradient of the eval-mode rear half
+    def _gate(self, name, dy, y, out):
+        """out = dy * [y > 0]: the backward of a ReLU, gated by the activation the eval forward keeps."""
+        assert dy.M == y.M == out.M and dy.C == y.C == out.C
+        self.op(self.pnp_bwd, name, self.L.rd_act_gate_t, self.dt, dy.ptr, dy.ld, y.ptr, y.ld, out.ptr, out.ld, C.c_int64(y.M), y.C, ACT_RELU,
+                self.stream)
+        return out
+
+    def _pnp_dgrad(self, c, dout, dx=None):
+        """Input gradient of a folded convolution of the rear half (context from _pnp_operand): dout -> dx, no weight gradient."""
+        x = c["x"]
+        if dx is None:
+            dx = self.act(x.N, x.H, x.W, x.C)
+        dd, zero_fill = self._desc(c["kind"], True, x, c["cout"], c["k"], c["stride"], c["pad"], ld_dy=dout.ld, ld_dx=dx.ld)
+        assert not zero_fill, "the rear half has no strided convolution"
+        self.keep.append(dd)
+        fam = self._confirm_dgrad(c, dd, dout, dx, False, zero_fill)
+        self._launch_conv(self.pnp_bwd, c["name"] + ".dgrad", fam, dd, dout, c["wd"], dx, c["k"])
+        self.taps["pnp_grad_in:" + c["name"]] = dx
+        return dx
+
+    def _upproj_pnp_bwd(self, ctx, dy, dx=None):
+        """Eval-mode backward of an UpProj module: y = relu(conv2'(R[:, :half]) + R[:, half:]) with R = conv5x5'(x), ReLU on R's upper
+        half only (primes: BatchNorm folded).  The residual add hands the gated gradient to both branches."""
+        name, half, R = ctx["name"], ctx["half"], ctx["R"]
+        dR = self.act(R.N, R.H, R.W, R.C)
+        g = self._gate(name + ".relu.gate", dy, ctx["y"], dR.chan(half, half))
+        dy1 = self._pnp_dgrad(ctx["c2"], g)
+        # (R[:, :half] is already post-ReLU in the eval forward: the 5x5 launch applies it to those columns)
+        self._gate(name + ".upper_branch.relu.gate", dy1, R.chan(0, half), dR.chan(0, half))
+        self.taps["pnp_grad_R:" + name] = dR
+        return self._pnp_dgrad(ctx["cR"], dR, dx=dx)
+
+    def _conv_bn_relu_pnp_bwd(self, ctx, dy, dx=None):
+        """Eval-mode backward of a DeConv / UpConv layer: gate (in place), then the folded convolution's input gradient."""
+        return self._pnp_dgrad(ctx["c"], self._gate(ctx["name"] + ".relu.gate", dy, ctx["y"], dy), dx=dx)
+
+    def _build_pnp_backward(self, ups):
+        """self.pnp_bwd: d loss / d pred (self.dpred) -> d loss / d z (self.pnp_g, z = the bn2 output self.pnp_z) through the eval-mode rear
+        half.  Bilinear resize and head as in training; per decoder layer, in reverse, ReLU gates and input gradients on the folded
+        weights.  No weight gradient, no BatchNorm sum, nothing of a parameter's .grad; one stream, no forks."""
+        m, N, z = self.m, self.N, self.z
+        assert self._s is self.streams[0]
+        layer_bwd = self._upproj_pnp_bwd if m.decoder._layer_kind == "upproj" else self._conv_bn_relu_pnp_bwd
+        self.dpred = self.buf(N, 1, self.Ho, self.Wo)
+        ddm = self.buf(N, z.H, z.W)
+        self.op(self.pnp_bwd, "bilinear.bwd", self.L.rd_bilinear_bwd, _p(self.dpred), N, self.Ho, self.Wo, _p(ddm), z.H, z.W, self.stream)
+        dz = self.act(N, z.H, z.W, z.C)
+        self.op(self.pnp_bwd, "conv3.dgrad", self.L.rd_head_conv_dgrad_t, self.dt, _p(m.conv3.weight), _p(ddm), N, z.H, z.W, z.C, dz.ptr, dz.ld,
+                self.stream)
+        self.taps["pnp_grad_out:decoder"] = dz
+        self.pnp_ddm = ddm
+        zl = self.pnp_z
+        self.pnp_g = self.act(zl.N, zl.H, zl.W, zl.C)
+        for i, ctx in reversed(list(enumerate(ups))):
+            dz = layer_bwd(ctx, dz, dx=self.pnp_g if i == 0 else None)
+        assert dz is self.pnp_g
 
     def _head(self, z):
         m, N = self.m, self.N
@@ -1381,8 +1477,8 @@ class LateFusionPlan:
                 or os.environ.get("RD_PY_LOOP") == "1")
 
     def run_list(self, key, begin=0, end=None):
-        """Issue ops [begin, end) of self.prep / self.fwd / self.bwd (key = "prep" | "fwd" | "bwd") with ONE C-ABI call: the three
-        lists are marshalled once into an op table (optable.py, rd_optable_run)."""
+        """Issue ops [begin, end) of self.prep / self.fwd / self.bwd (key = "prep" | "fwd" | "bwd"; "pnp_bwd" in pnp plans) with ONE
+        C-ABI call: the lists are marshalled once into an op table (optable.py, rd_optable_run)."""
         lst = getattr(self, key)
         end = len(lst) if end is None else end
         if self.dry_run:
@@ -1392,7 +1488,7 @@ class LateFusionPlan:
         if self._optable is None:
             from .optable import OpTable
             self._table_base, ops = {}, []
-            for k in ("prep", "fwd", "bwd"):
+            for k in ("prep", "fwd", "bwd") + (("pnp_bwd",) if self.pnp else ()):
                 self._table_base[k] = (len(ops), len(getattr(self, k)))
                 ops += getattr(self, k)
             self._optable = OpTable(self.L, ops, self.streams)
@@ -1468,6 +1564,37 @@ class LateFusionPlan:
             self.dpred.copy_(dpred)
         self.run_list("bwd")
 
+    # ---- the halves of a pnp plan (model.pnp_forward_front / pnp_forward_rear; main.HipPnPInference issues the same op ranges itself)
+    def run_front(self, x):
+        """x [N,>=C,H,W] fp32 CUDA -> the latent z = bn2(conv2(...)) as a fresh NCHW tensor."""
+        if tuple(x.shape[:1]) + tuple(x.shape[2:]) != (self.N, self.H, self.W) or x.shape[1] < self.x_in.shape[1]:
+            raise ValueError("plan built for [%d,>=%d,%d,%d], got %s" % (self.N, self.x_in.shape[1], self.H, self.W, tuple(x.shape)))
+        self.set_stream()
+        self.bind_own_input()
+        self.x_in.copy_(x[:, :self.x_in.shape[1]])
+        self.run_list("prep")
+        self.run_list("fwd", 0, self.rear_begin)
+        return self.pnp_z.view().permute(0, 3, 1, 2).contiguous()
+
+    def run_rear(self, z):
+        """z [N,256,h,w] fp32 CUDA (copied into the plan's latent buffer) -> the prediction, a fresh tensor."""
+        zl = self.pnp_z
+        if tuple(z.shape) != (zl.N, zl.C, zl.H, zl.W):
+            raise ValueError("plan built for a latent of [%d,%d,%d,%d], got %s" % (zl.N, zl.C, zl.H, zl.W, tuple(z.shape)))
+        self.set_stream()
+        self.generation += 1
+        zl.view().copy_(z.detach().float().permute(0, 2, 3, 1))
+        self.run_list("prep")           # (the folded operands follow the parameters: a rear without a front still packs them)
+        self.run_list("fwd", self.rear_begin)
+        return self.pred.clone()
+
+    def run_pnp_backward(self, dpred):
+        """d loss / d pred [N,1,Ho,Wo] -> d loss / d z as a fresh NCHW tensor (the activations of the last run_rear)."""
+        self.set_stream()
+        self.dpred.copy_(dpred)
+        self.run_list("pnp_bwd")
+        return self.pnp_g.view().permute(0, 3, 1, 2).contiguous()
+
 
 class ResNetPlan(LateFusionPlan):
     """The early-fusion network (models.py:233-303, ResNet.forward): ONE encoder on the network input's 1, 3 or 4 planes (modality d,
@@ -1476,12 +1603,12 @@ class ResNetPlan(LateFusionPlan):
     idle (its segment joins are empty edges).  fp32 tensors with split or fp32 operands."""
 
     def __init__(self, module, batch, height, width, train=True, dry_run=False, bf16=False, storage="fp32", segment_joins=True,
-                 autotune=None, split=False):
+                 autotune=None, split=False, pnp=False):
         if bf16 or storage == "bf16":
             raise NotImplementedError("the early-fusion ResNet plan serves fp32 tensors with split or fp32 operands: bf16 operands / "
                                       "bf16 storage are outside its scope")
         super().__init__(module, batch, height, width, train=train, dry_run=dry_run, segment_joins=segment_joins, autotune=autotune,
-                         split=split)
+                         split=split, pnp=pnp)
 
     def _build(self):
         m, N, H, W = self.m, self.N, self.H, self.W

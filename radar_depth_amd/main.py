@@ -6,6 +6,9 @@
                    zero_grad, backward, SGD step) fused on the device: no host synchronisation inside the step,
                    optional hipGraph replay, and -- when torch.distributed is initialised -- data-parallel
                    gradient averaging with bucketed RCCL all-reduces overlapped with the rest of backward.
+  HipInference  <- the validate() body main.py:564-595 (eval mode, batch 1) as one hipGraph
+  HipPnPInference  <- PnP-Depth refinement on the reference's pnp_forward_front / pnp_forward_rear halves (models.py:380-400,
+                   669-707): the whole sign-gradient loop on the latent as one hipGraph per frame
 """
 import ctypes as C
 import os
@@ -691,3 +694,219 @@ class HipInference:
         if self.multistage:
             return {"stage1": self.mp.p1.pred, "stage2": self.mp.p2.pred, "mask": self.mp.mask, "radar_filtered": self.mp.kept}
         return self.plans[0].pred
+
+
+class HipPnPInference:
+    """PnP-Depth refinement at test time (Wang et al., "Plug-and-Play: Improve Depth Estimation via Sparse Data Propagation") on the
+    reference's two halves (models.py:380-400, 669-707), in eval mode, as ONE hipGraph per frame:
+
+        z = front(x)                                 # encoder(s), conv2, bn2: once
+        for k in range(iters):
+            pred = rear(z)                           # decoder, conv3, bilinear resize
+            if k == iters - 1: break
+            loss_k = criterion(pred, sparse)         # masked by sparse > 0, mean over the valid pixels of the whole batch
+            z = z - alpha * sign(d loss_k / d z)
+
+    The gradient is the input gradient of the rear half on the folded eval weights (engine._build_pnp_backward): no weight gradient,
+    no BatchNorm sum, no parameter .grad.  iters = 1 is the plain prediction (HipInference's op list, bit for bit).  A batch without
+    a valid pixel leaves z unchanged (the gradient is all zero) and the losses NaN.  Nothing here synchronises with the host.
+
+    front(x), rear(), grad(sparse=None) and update() are the primitives __call__ is composed of; .z, .g and .pred are NCHW-shaped
+    views of the plan's buffers (.z writable), .losses a device tensor [iters - 1] that this object never reads back, .alpha settable."""
+
+    def __init__(self, model, batch, height, width, iters=5, alpha=0.01, criterion="l1", use_graph=True):
+        from .model.multistage_model import ResNet_multistage
+        if criterion not in ("l1", "l2"):
+            raise ValueError("HipPnPInference: criterion is 'l1' or 'l2', got %r" % (criterion,))
+        if int(iters) < 1:
+            raise ValueError("HipPnPInference: iters >= 1, got %r" % (iters,))
+        if isinstance(model, ResNet_multistage) or not hasattr(model, "pnp_forward_rear"):
+            raise NotImplementedError("PnP-Depth halves exist for ResNet_latefusion and ResNet_pnp (the reference defines none for %s)"
+                                      % type(model).__name__)
+        self.L = lib()
+        model.eval()
+        self.model, self.iters, self.criterion = model, int(iters), criterion
+        self.plan = p = model._plan(batch, height, width, False, pnp=True)
+        from .model.models import hold_plan
+        self._held = hold_plan(p, self)
+        if (p.Ho, p.Wo) != (height, width):
+            raise ValueError("PnP-Depth compares the prediction with the sparse input plane: output_size %s must be the input size %s"
+                             % ((p.Ho, p.Wo), (height, width)))
+        dev = p.dev
+        self.n_out = batch * p.Ho * p.Wo
+        self.sparse = torch.zeros(batch, 1, p.Ho, p.Wo, device=dev)          # contiguous copy of the sparse plane
+        self._alpha = float(alpha)
+        self.alpha_dev = torch.full((1,), float(alpha), device=dev)
+        tiles = self.L.rd_loss_tiles(C.c_int64(self.n_out))
+        self._ws = torch.zeros(2 * tiles, dtype=torch.float64, device=dev)
+        self._sums = torch.zeros(self.iters, 2, dtype=torch.float64, device=dev)
+        self._coef = torch.zeros(1, device=dev)
+        self._loss_all = torch.zeros(self.iters, device=dev)                 # (one spare slot: grad() behind the last rear())
+        self.losses = self._loss_all[:self.iters - 1]
+        self.z = p.pnp_z.view().permute(0, 3, 1, 2)
+        self.g = p.pnp_g.view().permute(0, 3, 1, 2)
+        self.pred = p.pred
+        self.use_graph = use_graph
+        self.graph = None
+        self.calls = 0
+        self._k = 0                    # refinement step the primitives are at: front() resets it, update() advances it
+        self._table = self._ops = None
+        self.side = torch.cuda.Stream(device=dev)
+
+    # ---- the loop as one op list: prep, fwd (front | rear), then per step k: grad_k, update, rear; a spare grad behind the end
+    def _grad_ops(self, k):
+        p, s, L, n = self.plan, self.plan.streams[0], self.L, C.c_int64(self.n_out)
+        sums = C.c_void_p(self._sums.data_ptr() + 16 * k)
+        loss = C.c_void_p(self._loss_all.data_ptr() + 4 * k)
+        f_sums, f_bwd = [getattr(L, "rd_masked_%s_%s" % (self.criterion, q)) for q in ("sums", "bwd")]
+        return [("pnp%d.loss.sums" % k, f_sums, (ptr(p.pred), ptr(self.sparse), n, ptr(self._ws), sums, s)),
+                ("pnp%d.loss.total" % k, L.rd_l1_total, (sums, loss, ptr(self._coef), s)),
+                ("pnp%d.loss.bwd" % k, f_bwd, (ptr(p.pred), ptr(self.sparse), n, sums, ptr(self._coef), ptr(p.dpred), 0, s))] + list(p.pnp_bwd)
+
+    def _update_ops(self):
+        z, g = self.plan.pnp_z, self.plan.pnp_g
+        return [("pnp.update", self.L.rd_pnp_update, (z.ptr, z.ld, g.ptr, g.ld, C.c_int64(z.M), z.C, ptr(self.alpha_dev), self.plan.streams[0]))]
+
+    def _build_table(self):
+        from .optable import OpTable
+        p = self.plan
+        ops, r = [], {}
+
+        def add(key, lst):
+            r[key] = (len(ops), len(ops) + len(lst))
+            ops.extend(lst)
+        add("front", list(p.prep) + list(p.fwd[:p.rear_begin]))
+        add("rear", list(p.fwd[p.rear_begin:]))
+        for k in range(self.iters - 1):
+            add("grad%d" % k, self._grad_ops(k))
+            add("update%d" % k, self._update_ops())
+            add("rear%d" % k, list(p.fwd[p.rear_begin:]))
+        r["loop"] = (0, len(ops))
+        add("grad%d" % (self.iters - 1), self._grad_ops(self.iters - 1))
+        add("update%d" % (self.iters - 1), self._update_ops())
+        self._ops, self._ranges = ops, r
+        self._table = OpTable(self.L, ops, list(p.streams))
+
+    def _issue(self, key):
+        if self._table is None:
+            self._build_table()
+        b, e = self._ranges[key]
+        if self.plan._diagnostic_loop():
+            return self.plan._run(self._ops[b:e])
+        self._table.run(b, e)
+
+    class _OnSide:
+        def __init__(self, owner):
+            self.o = owner
+
+        def __enter__(self):
+            o = self.o
+            self.caller = torch.cuda.current_stream()
+            o.side.wait_stream(self.caller)
+            self.cm = torch.cuda.stream(o.side)
+            self.cm.__enter__()
+            o.plan.set_stream()
+            o.plan.bind_own_input()
+
+        def __exit__(self, *exc):
+            self.cm.__exit__(*exc)
+            self.caller.wait_stream(self.o.side)
+
+    def _load(self, x, sparse):
+        """Copy the frame (and its sparse plane) into the static buffers; sparse=None: the plane the network reads as radar depth."""
+        p = self.plan
+        if x is not None:
+            cin = p.x_in.shape[1]
+            if tuple(x.shape[:1]) + tuple(x.shape[2:]) != (p.N, p.H, p.W) or x.shape[1] < cin:
+                raise ValueError("HipPnPInference was built for inputs [%d,>=%d,%d,%d], got %s" % (p.N, cin, p.H, p.W, tuple(x.shape)))
+            if sparse is None and cin == 3:
+                raise ValueError("an rgb network reads no sparse depth plane: pass sparse=")
+            p.x_in.copy_(x[:, :cin])
+            if sparse is None:
+                sparse = x[:, 3:4] if cin == 4 else x[:, 0:1]
+        if sparse is not None:
+            if tuple(sparse.shape) != tuple(self.sparse.shape):
+                raise ValueError("sparse must be %s, got %s" % (tuple(self.sparse.shape), tuple(sparse.shape)))
+            self.sparse.copy_(sparse)
+
+    @property
+    def alpha(self):
+        return self._alpha
+
+    @alpha.setter
+    def alpha(self, v):
+        self._alpha = float(v)
+        self.alpha_dev.fill_(float(v))       # (a device fill on the caller's stream: the graph reads the value when it runs)
+
+    @property
+    def last_loss(self):
+        """The loss of the latest grad(): a one-element device view."""
+        k = self._k % self.iters
+        return self._loss_all[k:k + 1]
+
+    # ---- primitives
+    def front(self, x, sparse=None):
+        """x -> z (encoder(s), conv2, bn2); also lays down the sparse plane grad() compares with."""
+        with self._OnSide(self):
+            self._load(x, sparse)
+            self.plan.generation += 1
+            self._issue("front")
+            self._k = 0
+        return self.z
+
+    def rear(self):
+        """z -> pred (decoder, conv3, bilinear resize)."""
+        with self._OnSide(self):
+            self.plan.generation += 1
+            self._issue("rear")
+        return self.pred
+
+    def grad(self, sparse=None):
+        """g = d criterion(pred, sparse) / d z for the pred of the latest rear(); the loss goes to losses[k], k counting update()s."""
+        with self._OnSide(self):
+            self._load(None, sparse)
+            self._issue("grad%d" % (self._k % self.iters))
+        return self.g
+
+    def update(self):
+        """z = z - alpha * sign(g)."""
+        with self._OnSide(self):
+            self._issue("update%d" % (self._k % self.iters))
+            self._k += 1
+        return self.z
+
+    def __call__(self, x, sparse=None):
+        """x [B,>=C,H,W] CUDA fp32, sparse [B,1,H,W] or None -> the refined prediction (a plan-owned tensor, valid until the next call)."""
+        with self._OnSide(self):
+            p = self.plan
+            self._load(x, sparse)
+            p.generation += 1
+            if self._table is None:
+                self._build_table()
+            if self.use_graph and self.calls >= 1 and self.graph is None and not p._diagnostic_loop():
+                check(self.L.rd_graph_begin(p.streams[0]), "graph_begin")
+                self._issue("loop")
+                g = C.c_void_p(0)
+                check(self.L.rd_graph_end(p.streams[0], C.byref(g)), "graph_end")
+                self.graph = g
+            if self.graph is not None:
+                check(self.L.rd_graph_launch(self.graph, p.streams[0]), "graph_launch")
+            else:
+                self._issue("loop")
+            self.calls += 1
+            self._k = self.iters - 1
+        return self.pred
+
+    def close(self):
+        g, self.graph = getattr(self, "graph", None), None
+        if g is not None:
+            self.L.rd_graph_destroy(g)
+        tb, self._table = getattr(self, "_table", None), None
+        if tb is not None:
+            tb.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -13,7 +13,9 @@ hand-written HIP kernels through the C ABI (include/radar_depth_hip.h):
   * there is NO CPU / PyTorch fallback: calling forward on a CPU tensor or without the built library raises.
 
 ResNet (models.py:233-303) is the single-encoder, early-fusion network of `--arch resnet18 / resnet34` (modality rgb, rgbd or d).
-Out of scope here (other --arch choices of the reference): ResNet_pnp, ResNet2, ResNet_multifusion, the Bottleneck depths of ResNet.  Of the
+ResNet_pnp (models.py:306-400) is that network plus the two halves of PnP-Depth refinement, pnp_forward_front / pnp_forward_rear,
+which ResNet_latefusion carries too (models.py:669-707): _PnPHalves below.
+Out of scope here (other --arch choices of the reference): ResNet2, ResNet_multifusion, the Bottleneck depths of ResNet.  Of the
 decoders, DeConv serves kernel sizes 2 and 3 (`deconv2`, `deconv3`); `choose_decoder` raises NotImplementedError for larger ones.
 """
 import math
@@ -407,7 +409,63 @@ def choose_decoder(decoder, in_channels):
         assert False, "invalid option for decoder: {}".format(decoder)
 
 
-class ResNet_latefusion(ArenaOwner, nn.Module):
+class _PnPRearFunction(torch.autograd.Function):
+    """pnp_forward_rear behind torch.autograd: backward is the plan's pnp_bwd op list (engine._build_pnp_backward) -- the input
+    gradient of the eval-mode rear half w.r.t. the latent, and nothing else: no parameter gradient exists on this route."""
+
+    @staticmethod
+    def forward(ctx, plan, z):
+        ctx.plan = hold_plan(plan, ctx)
+        out = plan.run_rear(z)
+        ctx.generation = plan.generation
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        plan = ctx.plan
+        if plan.generation != ctx.generation:
+            raise RuntimeError("this plan ran another forward since the pnp_forward_rear being differentiated: its activations are static "
+                               "buffers, so take the gradient before the next pnp_forward_rear of the same (batch, size)")
+        return None, plan.run_pnp_backward(gout.contiguous().float())
+
+
+class _PnPHalves:
+    """Mixin: the reference's two halves of PnP-Depth refinement (models.py:380-400, 669-707) on an eval-mode HIP plan.
+    pnp_forward_front(x) runs the encoder(s), conv2 and bn2 and returns the latent z; pnp_forward_rear(z) runs the decoder, conv3 and
+    the bilinear resize, and is differentiable w.r.t. z (first order): torch.autograd.grad(criterion(pred, sparse), z) runs the
+    rear half's input gradient in HIP.  NCHW CUDA tensors in and out.  Eval mode only: the gradient goes through the running
+    statistics (BatchNorm folded into the convolutions), which is what the reference computes under model.eval()."""
+
+    def _pnp_check(self, x, what):
+        if self.training:
+            raise RuntimeError("%s runs in eval mode only (call model.eval()): PnP-Depth refines a prediction on running statistics" % what)
+        if not x.is_cuda:
+            raise RuntimeError("radar_depth_amd modules run on MI355X only (HIP kernels); got a %s tensor" % x.device.type)
+        assert x.dim() == 4
+
+    def pnp_forward_front(self, x):
+        self._pnp_check(x, "pnp_forward_front")
+        plan = self._plan(x.shape[0], x.shape[2], x.shape[3], False, pnp=True)
+        return plan.run_front(x.contiguous().float())
+
+    def pnp_forward_rear(self, x):
+        self._pnp_check(x, "pnp_forward_rear")
+        # the latent does not name the input size (five halvings): the plan is the most recent pnp plan whose latent has this shape
+        # (the one pnp_forward_front just ran on), else the one of an input as large as the output
+        h, w = self.output_size
+        version = self._ensure_arenas()["version"]
+        for key, pl in reversed(list(self.__dict__.get("_plans", {}).items())):
+            if key[-1] is True and key[4] == version and (pl.N, pl.pnp_z.C, pl.pnp_z.H, pl.pnp_z.W) == tuple(x.shape):
+                h, w = key[1], key[2]
+                break
+        plan = self._plan(x.shape[0], h, w, False, pnp=True)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _PnPRearFunction.apply(plan, x)
+        return plan.run_rear(x)
+
+
+class ResNet_latefusion(_PnPHalves, ArenaOwner, nn.Module):
     def __init__(self, layers, decoder, output_size, in_channels=4, pretrained=True):
         if layers not in _DEPTHS:
             raise RuntimeError("Only 18, 34, 50, 101, and 152 layer model are defined for ResNet. Got {}".format(layers))
@@ -474,16 +532,17 @@ class ResNet_latefusion(ArenaOwner, nn.Module):
         return 1
 
     # ------------------------------------------------------------------ HIP execution
-    def _plan(self, batch, height, width, train, depth_planes=None, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False):
+    def _plan(self, batch, height, width, train, depth_planes=None, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False,
+              pnp=False):
         from ..engine import LateFusionPlan
         st = self._ensure_arenas()
         key = (batch, height, width, bool(train), st["version"], None if depth_planes is None else tuple(t.data_ptr() for t in depth_planes),
-               bool(bf16), storage, bool(segment_joins), bool(split))
+               bool(bf16), storage, bool(segment_joins), bool(split), bool(pnp))
         plans = self.__dict__.setdefault("_plans", {})
         if key not in plans:
             _evict_plans(plans, st["version"])
             plans[key] = LateFusionPlan(self, batch, height, width, train=train, depth_planes=depth_planes, bf16=bf16, storage=storage,
-                                        segment_joins=segment_joins, autotune=autotune, split=split)
+                                        segment_joins=segment_joins, autotune=autotune, split=split, pnp=pnp)
         else:
             plans[key] = plans.pop(key)          # most recently used last
         return plans[key]
@@ -569,17 +628,18 @@ class ResNet(ArenaOwner, nn.Module):
         self.load_state_dict({k: v for k, v in sd.items() if k.split(".")[0] in tops and k in own}, strict=False)
 
     # ------------------------------------------------------------------ HIP execution
-    def _plan(self, batch, height, width, train, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False):
+    def _plan(self, batch, height, width, train, bf16=False, storage="fp32", segment_joins=True, autotune=None, split=False, pnp=False):
         from ..engine import ResNetPlan
         if bf16 or storage == "bf16":
             raise NotImplementedError("the early-fusion ResNet plan serves fp32 tensors with split or fp32 operands: bf16 operands / "
                                       "bf16 storage are outside its scope")
         st = self._ensure_arenas()
-        key = (batch, height, width, bool(train), st["version"], None, False, storage, bool(segment_joins), bool(split))
+        key = (batch, height, width, bool(train), st["version"], None, False, storage, bool(segment_joins), bool(split), bool(pnp))
         plans = self.__dict__.setdefault("_plans", {})
         if key not in plans:
             _evict_plans(plans, st["version"])
-            plans[key] = ResNetPlan(self, batch, height, width, train=train, segment_joins=segment_joins, autotune=autotune, split=split)
+            plans[key] = ResNetPlan(self, batch, height, width, train=train, segment_joins=segment_joins, autotune=autotune, split=split,
+                                    pnp=pnp)
         else:
             plans[key] = plans.pop(key)          # most recently used last
         return plans[key]
@@ -595,6 +655,11 @@ class ResNet(ArenaOwner, nn.Module):
         if self.training and torch.is_grad_enabled():
             return _PlanFunction.apply(plan, x, *self._arena_root()._ensure_arenas()["params"])
         return plan.run_forward(x).clone()
+
+
+class ResNet_pnp(_PnPHalves, ResNet):
+    """The reference's ResNet_pnp (models.py:306-400): the early-fusion ResNet -- same constructor, attribute names, state_dict keys
+    and forward -- plus pnp_forward_front / pnp_forward_rear.  Layers 18 / 34 and 1, 3 or 4 input planes, as ResNet."""
 
 
 class _PlanFunction(torch.autograd.Function):
