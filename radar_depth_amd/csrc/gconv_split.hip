@@ -18,8 +18,8 @@
 //               beside the other waves' MFMAs; inside one wave they would sit between MFMA bursts).
 //   LDS       : patch [piece][pixel][16 + 8] bf16 (pixel pitch 48 B: the 16 lanes of a b128 read pass fall into 16 bank groups), two
 //               buffers of it where they fit (PDB: the 2 x 2 tile); weights [ring of 3][piece][3 taps][2][BN] x 16 B, staged in
-//               groups of three taps (all nine at once x 3 pieces x 2 buffers = 110 KB); a phase's last group is padded with
-//               zero-weight taps, so every group is three MFMA steps.
+//               groups of three taps (all nine at once x 3 pieces x 2 buffers = 110 KB); a phase's last group holds the one or two
+//               taps that are left and runs only their MFMA steps (its other tap slots are neither written nor read).
 //   loop      : one barrier per (16-channel chunk, tap group); it publishes the NEXT group's weights (issued a group earlier), so the
 //               compute waves read that group's first fragments before the barrier and continue straight behind it.  The patch of
 //               the next chunk is fetched a chunk ahead, split in its second group and stored in its last one -- into the other
@@ -132,6 +132,29 @@ __device__ __forceinline__ void split8(const float4 v0, const float4 v1, sbf16x8
     p2 = __builtin_bit_cast(sbf16x8, w2);
 }
 
+// Tap groups of one, two or three steps are separate bodies behind wave-uniform tests of the step count.  Each test reads the count
+// through an empty asm, so that the compiler sees three independent `if`s and does not thread them back into one if / else chain.
+__device__ __forceinline__ bool gs_steps_are(int nsteps, int n) {
+    asm volatile("" : "+s"(nsteps));
+    return nsteps == n;
+}
+
+// A one-step tap group skips the step that would have overwritten the second fragment set.  The set's values are dead when a group
+// starts, but the compiler cannot know: it would carry them around the loop next to the accumulators (both sets alive across the
+// back edge: +24..60 registers, spills on the larger tiles).  An output-only empty asm, at the top of every group, redefines them
+// at no instruction.
+template <int N>
+__device__ __forceinline__ void frag_dead(sbf16x8 (&F)[3][N]) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            su32x4 u;
+            asm volatile("" : "=v"(u));
+            F[p][i] = __builtin_bit_cast(sbf16x8, u);
+        }
+}
+
 // PRE: the input was split by its producer (piece planes in HBM): the staging waves issue nothing but global_load_lds copies -- patch
 // rows land as [piece][8-channel unit][patch pixel] x 16 B (lane-linear: consecutive pixels in consecutive 16-byte slots, which is
 // also what keeps the compute waves' ds_read_b128 passes conflict-free), out-of-image positions are zeroed once per workgroup and
@@ -171,7 +194,7 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
     const int PH = (th_n - 1) * IS + (P.dh_max - P.dh_min) + 1;
     const int ih0 = r0 * IS + P.dh_min, iw0 = c0 * IS + P.dw_min;
     const int ntaps = __builtin_amdgcn_readfirstlane(P.n_taps);
-    const int ngroups = (ntaps + GS_TPS - 1) / GS_TPS;      // the last group is padded with zero-weight taps: every group is 3 steps
+    const int ngroups = (ntaps + GS_TPS - 1) / GS_TPS;      // the last group of a phase may be short: ntaps - tap0 = 1 or 2 steps
     const int co0 = cot * BN;
 
     // LDS carve-up
@@ -322,7 +345,7 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
 #pragma unroll
                         for (int p = 0; p < 3; ++p)
                             glds16(reinterpret_cast<const float*>(src + p * a.wplane + go), reinterpret_cast<float*>(dst + p * WPP + (e - lane) * 16));
-                    } else {                             // padding taps of the last group, output channels beyond Cout
+                    } else if (t < ntaps) {              // output channels beyond Cout (tap slots t >= ntaps of a short last group are never read)
                         // (inline assembly: a plain LDS store behind outstanding global_load_lds copies makes the compiler wait for them)
                         const su32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -478,8 +501,7 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
         for (int mt = 0; mt < MT; ++mt)
             aoffB[mt] = PRE ? s_apix[(wm * MT + mt) * 32 + l31] * 16 + hh * a.kplane : s_apix[(wm * MT + mt) * 32 + l31] * GS_PSB + hh * 16;
         const int boffB = (hh * BN + l31) * 16;
-        // tap offsets in the lanes of one VGPR, fetched with v_readlane (an s_load in the walk would force lgkmcnt(0) waits);
-        // the padding taps of the last group read tap 0's pixels against zero weights
+        // tap offsets in the lanes of one VGPR, fetched with v_readlane (an s_load in the walk would force lgkmcnt(0) waits)
         const int tapv = a.tapoff[ph][lane < ntaps ? lane : 0];
         // fragment addresses: A = patch plane p, this lane's pixel of M-tile mt (+ the tap's offset, wave-uniform, added per
         // step); B = one base per ring buffer, everything else (piece, tap of the group, N-tile) is an immediate
@@ -565,6 +587,15 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
                 if (!have) load(pbase, wb, min(tap0, ntaps - 1), 0, fa[P0], fb[P0]);
                 else if constexpr (PRE) loadB(wb, 0, fb[P0]);
             }
+            // a phase's last group holds ntaps - tap0 = 1..3 taps: the short forms below run only those steps (their fragment reads and
+            // MFMAs), each a body of its own behind a wave-uniform branch -- the three-step bodies keep their basic blocks, and with them
+            // the read / MFMA interleaving.  A short group is the last of its chunk: it prefetches nothing (pref is false), so no
+            // fragment state crosses it.  Barriers, the weight ring and the patch protocol do not know about the step count.
+            // The three forms are three `if`s in a row, not an if / else chain (gs_steps_are): the accumulators then pass every join
+            // as (unchanged | updated in place); through the flow blocks of a structurised chain they got a second register set.
+            const int nsteps = ntaps - tap0;
+            if constexpr (MT == 3 && NT == 2) frag_dead(fb[PRE ? 1 : P1]);
+            else { frag_dead(fa[P1]); frag_dead(fb[P1]); }
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (MT == 3 && NT == 2) {
                 // The 3 x 2 tile has no registers for two full fragment sets next to its 96 accumulators (the form below reads a step's
@@ -596,49 +627,77 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
                             __builtin_amdgcn_sched_barrier(0);
                         }
                 };
-                if constexpr (PRE) {
-                    rstep(fa[0], fb[0], fb[1], min(tap0 + 1, ntaps - 1), wb, 1, true, true);
-                    rstep(fa[0], fb[1], fb[0], min(tap0 + 2, ntaps - 1), wb, 2, true, true);
-                    rstep(fa[0], fb[0], fb[1], min(tap0 + 3, ntaps - 1), wb, 0, pref, false);
-                } else {      // (split while staging: the next group's weights were published by THIS group's barrier -- its first B is prefetched too)
-                    rstep(fa[0], fb[P0], fb[P1], min(tap0 + 1, ntaps - 1), wb, 1, true, true);
-                    rstep(fa[0], fb[P1], fb[P0], min(tap0 + 2, ntaps - 1), wb, 2, true, true);
-                    rstep(fa[0], fb[P0], fb[P1], min(tap0 + 3, ntaps - 1), wbn, 0, pref, pref);
+                constexpr int B0 = PRE ? 0 : P0, B1 = 1 - B0;      // B set of the group's first step
+                if (nsteps >= GS_TPS) {
+                    if constexpr (PRE) {
+                        rstep(fa[0], fb[0], fb[1], min(tap0 + 1, ntaps - 1), wb, 1, true, true);
+                        rstep(fa[0], fb[1], fb[0], min(tap0 + 2, ntaps - 1), wb, 2, true, true);
+                        rstep(fa[0], fb[0], fb[1], min(tap0 + 3, ntaps - 1), wb, 0, pref, false);
+                    } else {      // (split while staging: the next group's weights were published by THIS group's barrier -- its first B is prefetched too)
+                        rstep(fa[0], fb[P0], fb[P1], min(tap0 + 1, ntaps - 1), wb, 1, true, true);
+                        rstep(fa[0], fb[P1], fb[P0], min(tap0 + 2, ntaps - 1), wb, 2, true, true);
+                        rstep(fa[0], fb[P0], fb[P1], min(tap0 + 3, ntaps - 1), wbn, 0, pref, pref);
+                    }
                 }
+                if (gs_steps_are(nsteps, 2)) {
+                    rstep(fa[0], fb[B0], fb[B1], tap0 + 1, wb, 1, true, true);
+                    rstep(fa[0], fb[B1], fb[B0], 0, wb, 0, false, false);
+                }
+                if (gs_steps_are(nsteps, 1)) rstep(fa[0], fb[B0], fb[B1], 0, wb, 0, false, false);
             } else if constexpr (MT * NT < 4 || (MT * NT == 4 && PDB)) {
-                load(pbase, wb, min(tap0 + 1, ntaps - 1), 1, fa[P1], fb[P1]);
-                mma(fa[P0], fb[P0]);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                load(pbase, wb, min(tap0 + 2, ntaps - 1), 2, fa[P0], fb[P0]);
-                mma(fa[P1], fb[P1]);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                if (pref) {
-                    if constexpr (PRE) loadA(pbase, min(tap0 + 3, ntaps - 1), fa[P1]);     // (the next group's weights are published by ITS barrier)
-                    else load(pbase, wbn, min(tap0 + 3, ntaps - 1), 0, fa[P1], fb[P1]);      // first step of the next group (same chunk)
+                if (nsteps >= GS_TPS) {
+                    load(pbase, wb, min(tap0 + 1, ntaps - 1), 1, fa[P1], fb[P1]);
                     mma(fa[P0], fb[P0]);
                     interleave();
-                } else {
-                    mma(fa[P0], fb[P0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    load(pbase, wb, min(tap0 + 2, ntaps - 1), 2, fa[P0], fb[P0]);
+                    mma(fa[P1], fb[P1]);
+                    interleave();
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (pref) {
+                        if constexpr (PRE) loadA(pbase, min(tap0 + 3, ntaps - 1), fa[P1]);     // (the next group's weights are published by ITS barrier)
+                        else load(pbase, wbn, min(tap0 + 3, ntaps - 1), 0, fa[P1], fb[P1]);      // first step of the next group (same chunk)
+                        mma(fa[P0], fb[P0]);
+                        interleave();
+                    } else {
+                        mma(fa[P0], fb[P0]);
+                    }
                 }
+                if (gs_steps_are(nsteps, 2)) {
+                    load(pbase, wb, tap0 + 1, 1, fa[P1], fb[P1]);
+                    mma(fa[P0], fb[P0]);
+                    interleave();
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P1], fb[P1]);
+                }
+                if (gs_steps_are(nsteps, 1)) mma(fa[P0], fb[P0]);
             } else {
                 // the 3 x 2 tile (and the single-buffered 2 x 2) has no registers for interleaved reads (96 accumulators + two
                 // fragment sets of 60 + the read addresses spill): its reads go out in front of each step's MFMAs
-                load(pbase, wb, min(tap0 + 1, ntaps - 1), 1, fa[P1], fb[P1]);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(fa[P0], fb[P0]);
-                __builtin_amdgcn_sched_barrier(0);
-                load(pbase, wb, min(tap0 + 2, ntaps - 1), 2, fa[P0], fb[P0]);
-                __builtin_amdgcn_sched_barrier(0);
-                mma(fa[P1], fb[P1]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (pref) {
-                    if constexpr (PRE) loadA(pbase, min(tap0 + 3, ntaps - 1), fa[P1]);
-                    else load(pbase, wbn, min(tap0 + 3, ntaps - 1), 0, fa[P1], fb[P1]);
+                if (nsteps >= GS_TPS) {
+                    load(pbase, wb, min(tap0 + 1, ntaps - 1), 1, fa[P1], fb[P1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P0], fb[P0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    load(pbase, wb, min(tap0 + 2, ntaps - 1), 2, fa[P0], fb[P0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P1], fb[P1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (pref) {
+                        if constexpr (PRE) loadA(pbase, min(tap0 + 3, ntaps - 1), fa[P1]);
+                        else load(pbase, wbn, min(tap0 + 3, ntaps - 1), 0, fa[P1], fb[P1]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P0], fb[P0]);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                mma(fa[P0], fb[P0]);
+                if (gs_steps_are(nsteps, 2)) {
+                    load(pbase, wb, tap0 + 1, 1, fa[P1], fb[P1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P0], fb[P0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    mma(fa[P1], fb[P1]);
+                }
+                if (gs_steps_are(nsteps, 1)) mma(fa[P0], fb[P0]);
             }
             __builtin_amdgcn_sched_barrier(0);
             have = pref;
@@ -823,7 +882,8 @@ __global__ __launch_bounds__(512) void gconv_split_kernel(const GsArgs a) {
 //               chunk's end and lands under the other workgroup's work); weights [2][piece][3 taps][2][BN] x 16 B, the next tap group's
 //               copy issued at the start of each group.
 //   loop      : per tap group: wait for the own copies, barrier, issue the next group's weights, three MFMA steps with the next step's
-//               fragment reads interleaved; per chunk one more barrier before the patch is overwritten.
+//               fragment reads interleaved (a phase's last group: the one or two steps its taps need); per chunk one more barrier
+//               before the patch is overwritten.
 template <int MT, int NT, int DBG = 0, bool BNB = false>      // DBG (diagnostics, tools/ablate_gconv_split.py): 1 no MFMAs, 2 no fragment reads -- compile-time: a
                                             // run-time test inside the step splits the basic block the read / MFMA interleaving lives in
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void gconv_sp2_kernel(const GsArgs a) {
@@ -941,7 +1001,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
                         glds16(reinterpret_cast<const float*>(src + p * a.wplane + go), reinterpret_cast<float*>(dst + p * WPP + (e - lane) * 16));
-                } else {
+                } else if (t < ntaps) {                  // output channels beyond Cout (tap slots t >= ntaps of a short last group are never read)
                     // (inline assembly: a plain LDS store behind outstanding global_load_lds copies makes the compiler wait for the copies)
                     const su32x4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -1031,19 +1091,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
         const bool pref = g + 1 < ngroups;    // the next group reads the same patch: its first A fragments are prefetched
         if (!haveA) loadA(min(tap0, ntaps - 1), fa[P0]);
         loadB(wb, 0, fb[P0]);
+        // a phase's last group holds ntaps - tap0 = 1..3 taps; the short forms are bodies of their own behind wave-uniform tests
+        // (the three-step body keeps its basic block: see DBG above), they prefetch nothing: the last group of a chunk has no
+        // successor.  Three `if`s in a row, not a chain: see the 8-wave kernel
+        const int nsteps = ntaps - tap0;
+        frag_dead(fa[P1]);
+        frag_dead(fb[P1]);
         __builtin_amdgcn_sched_barrier(0);
-        loadA(min(tap0 + 1, ntaps - 1), fa[P1]);
-        loadB(wb, 1, fb[P1]);
-        mma(fa[P0], fb[P0]);
-        interleave(0);
-        __builtin_amdgcn_sched_barrier(0);
-        loadA(min(tap0 + 2, ntaps - 1), fa[P0]);
-        loadB(wb, 2, fb[P0]);
-        mma(fa[P1], fb[P1]);
-        interleave(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (pref) loadA(min(tap0 + 3, ntaps - 1), fa[P1]);
-        mma(fa[P0], fb[P0]);
+        if (nsteps >= GS_TPS) {
+            loadA(min(tap0 + 1, ntaps - 1), fa[P1]);
+            loadB(wb, 1, fb[P1]);
+            mma(fa[P0], fb[P0]);
+            interleave(0);
+            __builtin_amdgcn_sched_barrier(0);
+            loadA(min(tap0 + 2, ntaps - 1), fa[P0]);
+            loadB(wb, 2, fb[P0]);
+            mma(fa[P1], fb[P1]);
+            interleave(0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (pref) loadA(min(tap0 + 3, ntaps - 1), fa[P1]);
+            mma(fa[P0], fb[P0]);
+        }
+        if (gs_steps_are(nsteps, 2)) {
+            loadA(tap0 + 1, fa[P1]);
+            loadB(wb, 1, fb[P1]);
+            mma(fa[P0], fb[P0]);
+            interleave(0);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(fa[P1], fb[P1]);
+        }
+        if (gs_steps_are(nsteps, 1)) mma(fa[P0], fb[P0]);
         __builtin_amdgcn_sched_barrier(0);
         haveA = pref;
         ++it;
