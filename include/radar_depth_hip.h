@@ -244,10 +244,13 @@ int rd_wgrad_plan_info(const RdConvDesc* d, int32_t* out);
 
 /* OIHW -> packed logical [slab][I][ldc] at column offset co_off (forward operand), or, with
  * transpose != 0, -> packed [slab][O.. as rows][I as columns] (dgrad operand: rows are the
- * forward output channels at row offset co_off, ldc >= I).  flip != 0 reverses the slab order
- * (kh,kw -> KH-1-kh, KW-1-kw).  The physical order interleaves the rows by four (see the
- * descriptor comment above); the row count must be a multiple of 4.  Replaces nothing in the
- * reference (layout glue). */
+ * forward output channels at row offset co_off in rows_total rows, ldc >= I).  The slab of tap
+ * (kh,kw) is kh*KW+kw.  The physical order interleaves the rows by four (see the descriptor
+ * comment above); the row count (I forward, rows_total transposed) must be a multiple of 4.
+ * A job that would write outside its operand is refused with RD_EINVAL before the launch:
+ * co_off < 0; forward co_off + O > ldc; transposed co_off + O > rows_total or I > ldc.
+ * Replaces nothing in the reference (layout glue).  tests/pack_ref.py restates every packed
+ * operand in numpy. */
 int rd_pack_weights(const float* w_oihw, float* packed, int32_t O, int32_t I, int32_t KH, int32_t KW,
                     int32_t ldc, int32_t co_off, int32_t rows_total, int32_t transpose, void* stream);
 
@@ -290,7 +293,7 @@ int rd_wgrad_bf16_plan_info(const RdConvDesc* d, int32_t* out);
 int rd_wgrad_bf16_trace_read(unsigned long long* host, int n_wg);
 
 /* bf16 operand of rd_gconv_bf16: same arguments, element (slab, row, col) at ((slab*R/8 + row/8)*ldc + col)*8 + row%8,
- * rounded to nearest even; the reduction dimension must be a multiple of 8. */
+ * rounded to nearest even; the reduction dimension must be a multiple of 8.  Same geometry refusals as rd_pack_weights. */
 int rd_pack_weights_bf16(const float* w_oihw, void* packed_bf16, int32_t O, int32_t I, int32_t KH, int32_t KW,
                          int32_t ldc, int32_t co_off, int32_t rows_total, int32_t transpose, void* stream);
 
@@ -298,8 +301,13 @@ int rd_pack_weights_bf16(const float* w_oihw, void* packed_bf16, int32_t O, int3
  *   struct { const float* src; float* dst; const float* scale; int32_t O, I, T(=KH*KW), ldc, off, rows_total,
  *            transpose, first_block, quad, scale_col; }
  *   scale (nullable): per-output-channel factor = folded BatchNorm scale (eval mode), indexed by the source's dim 0 (O), or by its
- *   dim 1 (I) when scale_col != 0 (the [Cin, Cout, k, k] weight of a transposed convolution); quad 1: row-interleaved gconv
- *   operand layout, 2: bf16 operand of rd_gconv_bf16, 0: plain [slab][row][col] (the 7x7 stem kernels)
+ *   dim 1 (I) when scale_col != 0 (the [Cin, Cout, k, k] weight of a transposed convolution); the fold is one fp32 multiply of the
+ *   source value before any rounding; quad 1: row-interleaved gconv operand layout, 2: bf16 operand of rd_gconv_bf16, 0: plain
+ *   [slab][row][col] (the 7x7 stem kernels), 3: the three-piece operand of rd_gconv_split -- three planes of the quad 2 layout, plane
+ *   stride T * R * ldc bf16 elements (R = I forward, rows_total transposed), plane p holding piece p of
+ *   p0 = bf16(x), p1 = bf16(x - p0), p2 = bf16(x - p0 - p1), every subtraction in fp32, every rounding to nearest even:
+ *   p0 + p1 + p2 == x exactly for 2^-60 <= |x| <= 2^60 and +-0, the range tests/test_pack_host.py proves it over (no piece is
+ *   subnormal there; the kernels' wider range is stated at rd_gconv_split)
  * (same meaning as rd_pack_weights' arguments); block_job_dev[b] = job index of block b, where job j owns blocks
  * [first_block, first_block + ceil(O*I*T / rd_pack_chunk())).  Both arrays are built once by the host plan. */
 int rd_pack_chunk(void);
@@ -802,8 +810,12 @@ int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t 
  * (csrc/wino_split.hip): 16 instead of 36 products per 2x2 output tile, each product rebuilt from six bf16 MFMA terms like
  * rd_gconv_split.  Replaces F.conv2d / its input gradient for the BasicBlock and UpProj conv2 layers
  * (/root/reference/model/models.py:96-112,203-206; cuDNN's own Winograd under cudnn.benchmark, /root/reference/main.py:11,47).
- *   rd_wino_pack      : U = G g G^T of an OIHW [O][I][3][3] tensor (fp64, rounded once to fp32, three bf16 pieces) in the kernel's
- *                       copy layout; flip = 1 packs the input-gradient operand (channels transposed, taps rotated by 180 degrees).
+ *   rd_wino_pack      : U = G g G^T of an OIHW [O][I][3][3] tensor (fp64: columns first, then rows, every half-sum 0.5 * (a +- b + c);
+ *                       rounded once to fp32, x; three bf16 pieces with p0 = the fp64 U rounded once to bf16 -- bf16(x) unless x lies
+ *                       exactly between two bf16 values, then the neighbour U lay nearer to --, p1 = bf16(x - p0),
+ *                       p2 = bf16(x - p0 - p1): p0 + p1 + p2 == x) in the kernel's copy layout
+ *                       [cot][chunk][pos 16][piece 3][k half 2][co 64][8 reduction channels]; flip = 1 packs the input-gradient
+ *                       operand (channels transposed, taps rotated by 180 degrees).
  *                       u_packed: rd_wino_packed_bytes(O, I, flip) bytes.
  *   rd_wino_conv3x3   : out[N,H,W,Cout (stride ldo)] = conv3x3(in[N,H,W,Cin (stride ldi)]) (+ addend); stat_partial (may be NULL):
  *                       [rd_wino_stat_tiles(N,H,W)][2][Cout] per-tile sum / sum of squares of the stored values, the BatchNorm

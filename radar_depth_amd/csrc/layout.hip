@@ -181,10 +181,26 @@ static int grid_for(int64_t n, int block) {
 }  // namespace rd
 using namespace rd;
 
+// The geometry of a single-tensor pack, refused before the launch when the job would write outside its operand: the columns
+// [co_off, co_off + O) of ldc (forward), the rows [co_off, co_off + O) of rows_total and the I columns of ldc (transposed).
+// (The pointers are looked at last: a geometry that passes is seen to pass without a launch.)
+#define RD_CHECK_PACK_GEOMETRY(what)                                                                                                      \
+    do {                                                                                                                                  \
+        RD_CHECK_ARG(co_off >= 0, what ": negative offset %d", co_off);                                                                   \
+        if (!transpose) {                                                                                                                 \
+            RD_CHECK_ARG((int64_t)co_off + O <= ldc, what ": columns [%d, %d) outside ldc %d", co_off, co_off + O, ldc);                  \
+        } else {                                                                                                                          \
+            RD_CHECK_ARG((int64_t)co_off + O <= rows_total, what ": rows [%d, %d) outside rows_total %d", co_off, co_off + O, rows_total); \
+            RD_CHECK_ARG(I <= ldc, what ": %d columns outside ldc %d", I, ldc);                                                           \
+        }                                                                                                                                 \
+    } while (0)
+
 extern "C" int rd_pack_weights(const float* w_oihw, float* packed, int32_t O, int32_t I, int32_t KH, int32_t KW,
                                int32_t ldc, int32_t co_off, int32_t rows_total, int32_t transpose, void* stream) {
-    RD_CHECK_ARG(w_oihw && packed && O > 0 && I > 0 && KH > 0 && KW > 0, "pack_weights: bad arguments");
+    RD_CHECK_ARG(O > 0 && I > 0 && KH > 0 && KW > 0, "pack_weights: bad arguments");
     RD_CHECK_ARG((transpose ? rows_total : I) % 4 == 0, "pack_weights: the reduction dimension must be a multiple of 4");
+    RD_CHECK_PACK_GEOMETRY("pack_weights");
+    RD_CHECK_ARG(w_oihw && packed, "pack_weights: null pointer");
     const int64_t total = (int64_t)O * I * KH * KW;
     hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        w_oihw, packed, O, I, KH * KW, ldc, co_off, rows_total, transpose);
@@ -194,8 +210,10 @@ extern "C" int rd_pack_weights(const float* w_oihw, float* packed, int32_t O, in
 
 extern "C" int rd_pack_weights_bf16(const float* w_oihw, void* packed_bf16, int32_t O, int32_t I, int32_t KH, int32_t KW,
                                     int32_t ldc, int32_t co_off, int32_t rows_total, int32_t transpose, void* stream) {
-    RD_CHECK_ARG(w_oihw && packed_bf16 && O > 0 && I > 0 && KH > 0 && KW > 0, "pack_weights_bf16: bad arguments");
+    RD_CHECK_ARG(O > 0 && I > 0 && KH > 0 && KW > 0, "pack_weights_bf16: bad arguments");
     RD_CHECK_ARG((transpose ? rows_total : I) % 8 == 0, "pack_weights_bf16: the reduction dimension must be a multiple of 8");
+    RD_CHECK_PACK_GEOMETRY("pack_weights_bf16");
+    RD_CHECK_ARG(w_oihw && packed_bf16, "pack_weights_bf16: null pointer");
     const int64_t total = (int64_t)O * I * KH * KW;
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(grid_for(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        w_oihw, static_cast<__bf16*>(packed_bf16), O, I, KH * KW, ldc, co_off, rows_total, transpose);

@@ -371,8 +371,8 @@ epilogue:
     }
 }
 
-// U = G g G^T of every (reduction channel, output channel) pair in fp64, rounded once to fp32, split into three bf16 pieces, in the
-// layout the MFMA waves read as fragments: [cot][chunk][pos 16][piece 3][k half 2][co 64][8 reduction channels].
+// U = G g G^T of every (reduction channel, output channel) pair in fp64, rounded once to fp32 (x), split into three bf16 pieces that add up
+// to x -- p0 = the fp64 U rounded once to bf16, p1 = bf16(x - p0), p2 = bf16(x - p0 - p1) --, in the layout the MFMA waves read as fragments: [cot][chunk][pos 16][piece 3][k half 2][co 64][8 reduction channels].
 // flip = 0: forward (reduction = the I of OIHW, output = O); flip = 1: input gradient (reduction = O, output = I, taps rotated by 180 degrees).
 __device__ __forceinline__ void wino_pack_body(const float* __restrict__ w, int O, int I, int flip, unsigned short* __restrict__ u, int e) {
     const int R = flip ? O : I, Q = flip ? I : O;
@@ -406,7 +406,9 @@ __device__ __forceinline__ void wino_pack_body(const float* __restrict__ w, int 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float f = (float)uu[j];
-                const __bf16 p0 = (__bf16)f;
+                // p0 is the double rounded once to bf16: where f lies exactly between two bf16 values it is the neighbour the double lay
+                // nearer to, not the even one.  p1, p2 are the pieces of f - p0, so p0 + p1 + p2 == f (tests/pack_ref.py wino_u).
+                const __bf16 p0 = (__bf16)uu[j];
                 f -= (float)p0;
                 const __bf16 p1 = (__bf16)f;
                 f -= (float)p1;
