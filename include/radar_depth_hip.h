@@ -380,6 +380,35 @@ int rd_stem_dgrad_channel(const float* dout, const float* w_packed, int32_t N, i
 /* ---------------------------------------------------------------------------------------
  * BatchNorm2d (training mode) + activation + residual join
  * (torch.nn.BatchNorm2d defaults eps=1e-5 momentum=0.1; models.py:101-110,203-208).
+ *
+ * Conventions (tests/norm_ref.py restates them in float64; tests/test_gpu_norm_fp64.py holds the fp32 entry points to them):
+ *   - ReLU: y = z > 0 ? z : +0, gradient 1 where the output is > 0 and 0 elsewhere -- the gradient at an output of exactly 0 is 0, and
+ *     -0.0 counts as 0.  LeakyReLU(0.2): y = z > 0 ? z : 0.2f * z, gradient 1 where the output is > 0 and the slope 0.2f elsewhere --
+ *     the gradient at 0 (either sign) is the slope.  The forms that recompute the sign from x (rd_bn_bwd_reduce_x / _x2,
+ *     rd_bn_bwd_apply_x / _x2, the pool backward) evaluate the forward kernel's own fmaf(scale, x, shift) [+ fmaf(scale2, x2, shift2)],
+ *     so they see the bits the forward pass saw.
+ *   - Statistics: mean = s / count and var = max(q / count - mean^2, 0) with s, q the sums of x and x^2 over the tiles, both added
+ *     in double; invstd = 1 / sqrt(var + eps); scale = gamma * invstd; shift = beta - mean * gamma * invstd; each rounded to fp32
+ *     once.  running_mean = (1 - momentum) * running_mean + momentum * mean; running_var likewise with var * count / (count - 1),
+ *     and with var itself at count = 1; num_batches_tracked += 1 per call.  running_mean and running_var are given or NULL
+ *     together; num_batches_tracked may be NULL or given independently of them.
+ *   - Backward: with S0 = sum g and Sw = sum g * (x_which - mean_which) over the tiles (double), dbeta = S0,
+ *     dgamma = invstd * Sw, and dx = A * g + B * (x - mean) + K with A = gamma * invstd, B = -gamma * invstd^3 * Sw / M,
+ *     K = -A * S0 / M (coef_ws = [A | B | K], each C floats); evaluated as fmaf(A, g, fmaf(B, x - mean, K)).
+ *   - Tile geometry: thread t of a 256-thread block owns channel quad t % (C/4) and row lane t / (C/4); there are
+ *     RL = 256 / (C/4) row lanes (threads beyond RL * C/4 idle when C/4 does not divide 256).  A block of rd_bn_stats covers
+ *     rows_per_block(M) = max(64, ceil(M / 2048)) rows, a block of the backward reductions
+ *     bwd_rows_per_block(M, C) = max(min(64, 4 * RL), ceil(M / 2048)); each lane adds every RL-th row of the block in fp32, the RL
+ *     lane sums are added in fp32 through LDS, and that is one row of stat_partial / red_partial.  The longest fp32 summation chain
+ *     of a partial sum is therefore ceil(rows per block / RL) + RL + 1 operations (the last for the product).
+ *   - Accuracy of the training statistics degrades as 1 + mean^2 / var: the variance is a difference of two fp32-accumulated sums, so
+ *     with u = 2^-24 and chain as above,  |invstd - exact| / exact <= chain * u * (E[x^2] + 2 |mean| E|x|) / (2 (var + eps)).
+ *     The fused convolution epilogues accumulate the same two sums in their own order and are subject to the same growth.
+ *   - Refusals (RD_EINVAL, nothing launched, checked in this order: shape, strides, pointers).  Every launcher of this section refuses
+ *     C < 4, C % 4 != 0, M <= 0, n_tiles <= 0, N / H / W <= 0, which outside {1, 2}, a stride ld with ld % 4 != 0 or ld < C on an operand
+ *     that is given (rd_bn_finalize: c0 < 0 or c0 + C > ld), and a required pointer that is NULL.  rd_bn_stats and the reduce forms
+ *     refuse C > 1024; rd_bnact_maxpool_bwd_stats[_t] and rd_bnact_maxpool_bwd_apply_t refuse a C/4 that does not divide 256.  The
+ *     pool kernels take x, g / dx and idx with stride C; only the pooled tensors y and dy carry a stride.
  * ------------------------------------------------------------------------------------- */
 /* Reduce conv-epilogue partials [n_tiles][2][ld] over channels [c0, c0+C) -> mean / invstd, fused
  * scale = gamma*invstd and shift = beta - mean*scale; update running stats (unbiased var) and
@@ -442,7 +471,8 @@ int rd_bn_bwd_apply_x2(const float* dy, int32_t lddy, const float* x1, int32_t l
                        int32_t C, void* stream);
 
 /* MaxPool2d(3,2,1) fused with the stem's BN affine + activation (models.py:634-636,644-646):
- * y = maxpool(act(scale*x+shift)); idx = argmax position 0..8 in the window. */
+ * y = maxpool(act(scale*x+shift)); idx = argmax position kh*3+kw (0..8) in the window, positions outside the image skipped;
+ * among equal maxima the first in (kh, kw) order wins, as in ATen's CPU kernel. */
 int rd_bnact_maxpool_fwd(const float* x, const float* scale, const float* shift, int32_t act,
                          int32_t N, int32_t H, int32_t W, int32_t C, float* y, int32_t ldy,
                          uint8_t* idx, void* stream);

@@ -529,14 +529,22 @@ static int ew_grid(int64_t elems) {
     return (int)(g < 1 ? 1 : g);
 }
 
+// Argument checks shared by the launchers of this file (include/radar_depth_hip.h, "Refusals"): every launcher checks its shape
+// first, its strides next and its pointers last, and launches nothing unless all three pass.
+static inline bool quads_ok(int C) { return C >= 4 && C % 4 == 0; }
+// the stride of an operand that is present: whole float4s, and no narrower than the channel window it holds
+static inline bool ld_ok(const void* p, int ld, int C) { return !p || (ld % 4 == 0 && ld >= C); }
+
 }  // namespace rd
 using namespace rd;
 
 extern "C" int rd_bn_finalize(const float* stat_partial, int32_t n_tiles, int32_t ld, int32_t c0, int32_t C, int64_t count, const float* gamma,
                               const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                               int64_t* nbt, float* mean, float* invstd, float* scale, float* shift, void* stream) {
-    RD_CHECK_ARG(stat_partial && gamma && beta && mean && invstd && scale && shift && n_tiles > 0 && C > 0 && count > 0 &&
-                     c0 >= 0 && c0 + C <= ld, "bn_finalize: bad arguments");
+    RD_CHECK_ARG(n_tiles > 0 && quads_ok(C) && count > 0, "bn_finalize: bad shape (n_tiles %d, C %d)", n_tiles, C);
+    RD_CHECK_ARG(c0 >= 0 && ld % 4 == 0 && (int64_t)c0 + C <= ld, "bn_finalize: channels [%d, %d + %d) outside ld = %d", c0, c0, C, ld);
+    RD_CHECK_ARG(stat_partial && gamma && beta && mean && invstd && scale && shift && (!running_mean == !running_var),
+                 "bn_finalize: null pointer");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, static_cast<hipStream_t>(stream), stat_partial, n_tiles, ld, c0,
                        (double)count, gamma, beta, eps, momentum, running_mean, running_var, nbt, mean, invstd, scale, shift);
     RD_CHECK_LAUNCH("bn_finalize_kernel");
@@ -565,7 +573,9 @@ extern "C" int rd_bn_bwd_tiles(int64_t M, int32_t C) { return (C >= 4 && C % 4 =
 
 template <typename T>
 static int rd_bn_stats_T(const T* x, int64_t M, int32_t C, int32_t ldx, float* stat_partial, int32_t* n_tiles, void* stream) {
-    RD_CHECK_ARG(x && stat_partial && M > 0 && C >= 4 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0, "bn_stats: bad arguments");
+    RD_CHECK_ARG(M > 0 && quads_ok(C) && C <= 1024, "bn_stats: bad shape (C %d)", C);
+    RD_CHECK_ARG(ldx % 4 == 0 && ldx >= C, "bn_stats: bad stride %d", ldx);
+    RD_CHECK_ARG(x && stat_partial, "bn_stats: null pointer");
     const int RPB = rows_per_block(M), grid = (int)cdiv64(M, RPB);
     const int Q = C / 4, RL = 256 / Q;
     hipLaunchKernelGGL((bn_stats_kernel<T>), dim3(grid), dim3(256), (size_t)RL * 2 * C * sizeof(float),
@@ -588,8 +598,9 @@ extern "C" int rd_bn_stats_t(int32_t dtype, const void* x, int64_t M, int32_t C,
 template <typename T>
 static int rd_bn_act_T(const T* x1, int32_t ldx1, const float* scale1, const float* shift1, const T* x2, int32_t ldx2, const float* scale2, const float* shift2, T* y, int32_t ldy, int64_t M, int32_t C, int32_t act, void* stream,
                        void* pieces = nullptr, int64_t piece_elems = 0) {
-    RD_CHECK_ARG(x1 && scale1 && shift1 && y && M > 0 && C % 4 == 0 && ldx1 % 4 == 0 && ldy % 4 == 0 && (!x2 || ldx2 % 4 == 0),
-                 "bn_act: bad arguments");
+    RD_CHECK_ARG(M > 0 && quads_ok(C), "bn_act: bad shape (C %d)", C);
+    RD_CHECK_ARG(ldx1 % 4 == 0 && ldx1 >= C && ldy % 4 == 0 && ldy >= C && ld_ok(x2, ldx2, C), "bn_act: bad stride");
+    RD_CHECK_ARG(x1 && scale1 && shift1 && y && (!scale2 || (x2 && shift2)), "bn_act: null pointer");
     RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_act: bad piece planes");
     hipLaunchKernelGGL((bn_act_kernel<T>), dim3(ew_grid(M * (C / 4))), dim3(256), 0, static_cast<hipStream_t>(stream), x1, ldx1,
                        scale1, shift1, x2, ldx2, scale2, shift2, y, ldy, M, C, act, static_cast<unsigned short*>(pieces), piece_elems);
@@ -617,8 +628,13 @@ template <typename T>
 static int bn_bwd_reduce_impl(const T* dy, int32_t lddy, const T* y, int32_t ldy, const T* x1, int32_t ldx1,
                               const float* mean1, const T* x2, int32_t ldx2, const float* mean2, T* g, int32_t ldg,
                               int64_t M, int32_t C, int32_t act, float* red_partial, const float* scale1, const float* shift1,
-                              void* stream, const float* scale2 = nullptr, const float* shift2 = nullptr) {
-    RD_CHECK_ARG(dy && red_partial && M > 0 && C >= 4 && C % 4 == 0 && C <= 1024, "bn_bwd_reduce: bad arguments");
+                              void* stream, const float* scale2 = nullptr, const float* shift2 = nullptr, bool two_bn = false) {
+    RD_CHECK_ARG(M > 0 && quads_ok(C) && C <= 1024, "bn_bwd_reduce: bad shape (C %d)", C);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C && ld_ok(y, ldy, C) && ld_ok(x1, ldx1, C) && ld_ok(x2, ldx2, C) && ld_ok(g, ldg, C),
+                 "bn_bwd_reduce: bad stride");
+    RD_CHECK_ARG(dy && red_partial, "bn_bwd_reduce: null pointer");
+    // (rd_bn_bwd_reduce_x2: act(bn1(x1) + bn2(x2)) with the sign recomputed from both operands)
+    RD_CHECK_ARG(!two_bn || (x1 && x2 && scale1 && shift1 && scale2 && shift2 && act != RD_ACT_NONE), "bn_bwd_reduce_x2: bad arguments");
     RD_CHECK_ARG(act == RD_ACT_NONE || y || (scale1 && shift1 && x1 && (!x2 || (scale2 && shift2))),
                  "bn_bwd_reduce: activation needs y (or the scale/shift of every operand)");
     RD_CHECK_ARG((!x1 || mean1) && (!x2 || mean2), "bn_bwd_reduce: x without mean");
@@ -674,8 +690,10 @@ int launch_bn_bwd_coeffs(const float* red_partial, int n_tiles, int C, int which
 template <typename T>
 static int rd_bn_bwd_apply_T(const T* g, int32_t ldg, const T* x, int32_t ldx, const float* red_partial, int32_t n_tiles, int32_t which, const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta, float* coef_ws, T* dx, int32_t lddx, int64_t M, int32_t C, void* stream,
                              void* pieces = nullptr, int64_t piece_elems = 0) {
-    RD_CHECK_ARG(g && x && red_partial && gamma && mean && invstd && coef_ws && dx && (which == 1 || which == 2) && M > 0 &&
-                     C % 4 == 0, "bn_bwd_apply: bad arguments");
+    RD_CHECK_ARG((which == 1 || which == 2) && M > 0 && n_tiles > 0 && quads_ok(C), "bn_bwd_apply: bad shape (which %d, n_tiles %d, C %d)",
+                 which, n_tiles, C);
+    RD_CHECK_ARG(ldg % 4 == 0 && ldg >= C && ldx % 4 == 0 && ldx >= C && lddx % 4 == 0 && lddx >= C, "bn_bwd_apply: bad stride");
+    RD_CHECK_ARG(g && x && red_partial && gamma && mean && invstd && coef_ws && dx, "bn_bwd_apply: null pointer");
     RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_bwd_apply: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, which, (double)M, gamma, invstd,
@@ -704,9 +722,8 @@ extern "C" int rd_bn_bwd_apply_t(int32_t dtype, const void* g, int32_t ldg, cons
 // gradient -- the activation output is not read, the masked gradient is not written, dy is read once per pass.
 template <typename T>
 static int rd_bn_bwd_reduce_x2_T(const T* dy, int32_t lddy, const T* x1, int32_t ldx1, const float* mean1, const float* scale1, const float* shift1, const T* x2, int32_t ldx2, const float* mean2, const float* scale2, const float* shift2, int64_t M, int32_t C, int32_t act, float* red_partial, void* stream) {
-    RD_CHECK_ARG(x1 && x2 && scale1 && shift1 && scale2 && shift2 && act != RD_ACT_NONE, "bn_bwd_reduce_x2: bad arguments");
     return bn_bwd_reduce_impl<T>(dy, lddy, nullptr, 0, x1, ldx1, mean1, x2, ldx2, mean2, nullptr, 0, M, C, act, red_partial, scale1, shift1, stream,
-                              scale2, shift2);
+                              scale2, shift2, true);
 }
 extern "C" int rd_bn_bwd_reduce_x2(const float* dy, int32_t lddy, const float* x1, int32_t ldx1, const float* mean1, const float* scale1, const float* shift1, const float* x2, int32_t ldx2, const float* mean2, const float* scale2, const float* shift2, int64_t M, int32_t C, int32_t act, float* red_partial, void* stream) {
     return rd_bn_bwd_reduce_x2_T<float>(dy, lddy, x1, ldx1, mean1, scale1, shift1, x2, ldx2, mean2, scale2, shift2, M, C, act, red_partial, stream);
@@ -721,8 +738,11 @@ extern "C" int rd_bn_bwd_reduce_x2_t(int32_t dtype, const void* dy, int32_t lddy
 template <typename T>
 static int rd_bn_bwd_apply_x2_T(const T* dy, int32_t lddy, const T* x1, int32_t ldx1, const T* x2, int32_t ldx2, const float* red_partial, int32_t n_tiles, const float* gamma1, const float* mean1, const float* invstd1, const float* scale1, const float* shift1, const float* gamma2, const float* mean2, const float* invstd2, const float* scale2, const float* shift2, int32_t act, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, float* coef_ws6, T* dx1, int32_t lddx1, T* dx2, int32_t lddx2, int64_t M, int32_t C, void* stream,
                                 void* pieces1 = nullptr, int64_t piece_elems1 = 0, void* pieces2 = nullptr, int64_t piece_elems2 = 0) {
+    RD_CHECK_ARG(M > 0 && n_tiles > 0 && quads_ok(C), "bn_bwd_apply_x2: bad shape (n_tiles %d, C %d)", n_tiles, C);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C && ldx1 % 4 == 0 && ldx1 >= C && ldx2 % 4 == 0 && ldx2 >= C && lddx1 % 4 == 0 && lddx1 >= C &&
+                     lddx2 % 4 == 0 && lddx2 >= C, "bn_bwd_apply_x2: bad stride");
     RD_CHECK_ARG(dy && x1 && x2 && red_partial && gamma1 && gamma2 && mean1 && mean2 && invstd1 && invstd2 && scale1 && shift1 && scale2 &&
-                     shift2 && coef_ws6 && dx1 && dx2 && M > 0 && C % 4 == 0, "bn_bwd_apply_x2: bad arguments");
+                     shift2 && coef_ws6 && dx1 && dx2, "bn_bwd_apply_x2: null pointer");
     RD_CHECK_ARG((!pieces1 || piece_planes_ok(pieces1, piece_elems1, M, C)) && (!pieces2 || piece_planes_ok(pieces2, piece_elems2, M, C)), "bn_bwd_apply_x2: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, 1, (double)M, gamma1, invstd1, dgamma1, dbeta1,
@@ -755,8 +775,9 @@ extern "C" int rd_bn_bwd_apply_x2_t(int32_t dtype, const void* dy, int32_t lddy,
 template <typename T>
 static int rd_bn_bwd_apply_x_T(const T* dy, int32_t lddy, const T* x, int32_t ldx, const float* red_partial, int32_t n_tiles, const float* gamma, const float* mean, const float* invstd, const float* scale, const float* shift, int32_t act, float* dgamma, float* dbeta, float* coef_ws, T* dx, int32_t lddx, int64_t M, int32_t C, void* stream,
                                void* pieces = nullptr, int64_t piece_elems = 0) {
-    RD_CHECK_ARG(dy && x && red_partial && gamma && mean && invstd && scale && shift && coef_ws && dx && M > 0 && C % 4 == 0,
-                 "bn_bwd_apply_x: bad arguments");
+    RD_CHECK_ARG(M > 0 && n_tiles > 0 && quads_ok(C), "bn_bwd_apply_x: bad shape (n_tiles %d, C %d)", n_tiles, C);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C && ldx % 4 == 0 && ldx >= C && lddx % 4 == 0 && lddx >= C, "bn_bwd_apply_x: bad stride");
+    RD_CHECK_ARG(dy && x && red_partial && gamma && mean && invstd && scale && shift && coef_ws && dx, "bn_bwd_apply_x: null pointer");
     RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, M, C), "bn_bwd_apply_x: bad piece planes");
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, 1, (double)M, gamma, invstd, dgamma,
@@ -784,7 +805,9 @@ extern "C" int rd_bn_bwd_apply_x_t(int32_t dtype, const void* dy, int32_t lddy, 
 template <typename T>
 static int rd_bnact_maxpool_fwd_T(const T* x, const float* scale, const float* shift, int32_t act, int32_t N, int32_t H, int32_t W, int32_t C, T* y, int32_t ldy, uint8_t* idx, void* stream,
                                   void* pieces = nullptr, int64_t piece_elems = 0) {
-    RD_CHECK_ARG(x && scale && shift && y && idx && C % 4 == 0 && ldy % 4 == 0, "bnact_maxpool_fwd: bad arguments");
+    RD_CHECK_ARG(N > 0 && H > 0 && W > 0 && quads_ok(C), "bnact_maxpool_fwd: bad shape (%d, %d, %d, C %d)", N, H, W, C);
+    RD_CHECK_ARG(ldy % 4 == 0 && ldy >= C, "bnact_maxpool_fwd: bad stride %d", ldy);
+    RD_CHECK_ARG(x && scale && shift && y && idx, "bnact_maxpool_fwd: null pointer");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     RD_CHECK_ARG(!pieces || piece_planes_ok(pieces, piece_elems, (int64_t)N * Ho * Wo, C), "bnact_maxpool_fwd: bad piece planes");     // (planes are indexed by OUTPUT pixels)
     hipLaunchKernelGGL((bnact_maxpool_fwd_kernel<T>), dim3(ew_grid((int64_t)N * Ho * Wo * (C / 4))), dim3(256), 0,
@@ -808,7 +831,9 @@ extern "C" int rd_bnact_maxpool_fwd_t(int32_t dtype, const void* x, const float*
 
 template <typename T>
 static int rd_bnact_maxpool_bwd_T(const T* dy, int32_t lddy, const uint8_t* idx, const T* x, const float* scale, const float* shift, int32_t act, int32_t N, int32_t H, int32_t W, int32_t C, T* g, void* stream) {
-    RD_CHECK_ARG(dy && idx && x && scale && shift && g && C % 4 == 0 && lddy % 4 == 0, "bnact_maxpool_bwd: bad arguments");
+    RD_CHECK_ARG(N > 0 && H > 0 && W > 0 && quads_ok(C), "bnact_maxpool_bwd: bad shape (%d, %d, %d, C %d)", N, H, W, C);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C, "bnact_maxpool_bwd: bad stride %d", lddy);
+    RD_CHECK_ARG(dy && idx && x && scale && shift && g, "bnact_maxpool_bwd: null pointer");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL((bnact_maxpool_bwd_kernel<T>), dim3(ew_grid((int64_t)N * Ho * Wo * (C / 4))), dim3(256), 0,
                        static_cast<hipStream_t>(stream), dy, lddy, idx, x, scale, shift, act, N, H, W, C, Ho, Wo, g,
@@ -837,9 +862,11 @@ extern "C" int rd_bnact_maxpool_bwd_tiles(int32_t N, int32_t H, int32_t W, int32
 }
 template <typename T>
 static int rd_bnact_maxpool_bwd_stats_T(const T* dy, int32_t lddy, const uint8_t* idx, const T* x, const float* scale, const float* shift, int32_t act, int32_t N, int32_t H, int32_t W, int32_t C, T* g, const float* mean, float* red_partial, void* stream) {
-    RD_CHECK_ARG(dy && idx && x && scale && shift && mean && red_partial && C % 4 == 0 && lddy % 4 == 0,
-                 "bnact_maxpool_bwd_stats: bad arguments");      // (g may be NULL: sums only, see rd_bnact_maxpool_bwd_apply_t)
-    RD_CHECK_ARG(C >= 4 && 256 % (C / 4) == 0, "bnact_maxpool_bwd_stats: C/4 = %d must divide 256", C / 4);
+    RD_CHECK_ARG(N > 0 && H > 0 && W > 0 && quads_ok(C), "bnact_maxpool_bwd_stats: bad shape (%d, %d, %d, C %d)", N, H, W, C);
+    RD_CHECK_ARG(256 % (C / 4) == 0, "bnact_maxpool_bwd_stats: C/4 = %d must divide 256", C / 4);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C, "bnact_maxpool_bwd_stats: bad stride %d", lddy);
+    RD_CHECK_ARG(dy && idx && x && scale && shift && mean && red_partial,
+                 "bnact_maxpool_bwd_stats: null pointer");      // (g may be NULL: sums only, see rd_bnact_maxpool_bwd_apply_t)
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const int Q = C / 4, RL = 256 / Q;
     hipLaunchKernelGGL((bnact_maxpool_bwd_kernel<T>), dim3(ew_grid((int64_t)N * Ho * Wo * (C / 4))), dim3(256),
@@ -867,9 +894,12 @@ static int rd_bnact_maxpool_bwd_apply_T(const T* dy, int32_t lddy, const uint8_t
                                         int32_t act, int32_t N, int32_t H, int32_t W, int32_t C, const float* red_partial, int32_t n_tiles,
                                         const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
                                         float* coef_ws, T* dx, void* stream) {
-    RD_CHECK_ARG(dy && idx && x && scale && shift && red_partial && gamma && mean && invstd && coef_ws && dx && C % 4 == 0 && lddy % 4 == 0 &&
-                     n_tiles > 0, "bnact_maxpool_bwd_apply: bad arguments");
-    RD_CHECK_ARG(C >= 4 && 256 % (C / 4) == 0, "bnact_maxpool_bwd_apply: C/4 = %d must divide 256", C / 4);
+    RD_CHECK_ARG(N > 0 && H > 0 && W > 0 && n_tiles > 0 && quads_ok(C), "bnact_maxpool_bwd_apply: bad shape (%d, %d, %d, n_tiles %d, C %d)", N, H,
+                 W, n_tiles, C);
+    RD_CHECK_ARG(256 % (C / 4) == 0, "bnact_maxpool_bwd_apply: C/4 = %d must divide 256", C / 4);
+    RD_CHECK_ARG(lddy % 4 == 0 && lddy >= C, "bnact_maxpool_bwd_apply: bad stride %d", lddy);
+    RD_CHECK_ARG(dy && idx && x && scale && shift && red_partial && gamma && mean && invstd && coef_ws && dx,
+                 "bnact_maxpool_bwd_apply: null pointer");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, s, red_partial, n_tiles, C, 1, (double)((int64_t)N * H * W), gamma, invstd,
