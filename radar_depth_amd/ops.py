@@ -172,6 +172,22 @@ def gconv(desc, x, w_packed, out, addend=None, ld_add=0, stat=None):
     return out
 
 
+def gconv_fused(desc, x, w_packed, out, bias=None, act=0, act_cols=0, addend=None, ld_add=0):
+    """Inference form out = act_{co < act_cols}(conv + bias + addend): rd_gconv_fused, workspace handled as in gconv."""
+    _poison()
+    n = int(lib().rd_gconv_workspace_floats(C.byref(desc)))
+    if n < 0:
+        check(n, "rd_gconv_workspace_floats")
+    ws = None
+    if n > 0:
+        ws = _WS.get((n, out.device))
+        if ws is None:
+            ws = _WS[(n, out.device)] = torch.empty(n, dtype=torch.float32, device=out.device)
+    check(lib().rd_gconv_fused(C.byref(desc), ptr(x), ptr(w_packed), ptr(out), ptr(bias), act, act_cols, ptr(addend), ld_add, ptr(ws),
+                               current_stream()), "rd_gconv_fused")
+    return out
+
+
 def gconv_bnbwd(desc, dout, w_packed, dx, bn_x, ld_x, mean, scale, shift, act, red):
     """Input gradient + the BatchNorm-backward sums of the BatchNorm behind the convolution's forward input (rd_gconv_bnbwd)."""
     _poison()
