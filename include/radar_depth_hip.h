@@ -910,6 +910,17 @@ int rd_comm_destroy(void);
  * (bf16 values are widened on load, results rounded to nearest-even on store); per-channel statistics, coefficients, weights'
  * gradients and every reduction stay fp32 / fp64.  Strides are in elements.  The argument lists are those of the fp32 entry
  * points above with `dtype` in front and the tensors as void pointers.
+ * Rounding points under RD_DTYPE_BF16 (tests/norm_bf16_cases.py restates them, tests/test_gpu_norm_bf16.py holds the kernels to them):
+ *   - Every stored tensor element is the fp32 value in the register rounded ONCE; rd_bn_act_t and rd_bnact_maxpool_fwd_t round y after
+ *     the activation (and the pool's argmax is taken of the fp32 activations, before any rounding).
+ *   - The backward sums (rd_bn_bwd_reduce_t / _x_t / _x2_t, rd_bnact_maxpool_bwd_stats_t) are taken of the UNROUNDED fp32 g, whether
+ *     or not a rounded g is stored beside them; rd_bn_bwd_reduce_t reads the activation's sign from the STORED (rounded) y.
+ *   - rd_bn_bwd_apply_t computes dx from the g it is given: the STORED, rounded one.
+ *   - rd_bn_bwd_apply_x_t and rd_bn_bwd_apply_x2_t recompute g = dy * act' in registers and do NOT round it: under LeakyReLU (the
+ *     only activation whose factor makes g inexact in bf16) their dx differs from reduce + rd_bn_bwd_apply_t by that one rounding of
+ *     g -- the more accurate of the two, and consistent with the sums, which are those of the unrounded g in both.
+ *   - rd_bnact_maxpool_bwd_apply_t rounds the gathered g to bf16 before it forms dx: the two-pass form is bit-identical to
+ *     rd_bnact_maxpool_bwd_stats_t (g stored) followed by rd_bn_bwd_apply_t.
  * ------------------------------------------------------------------------------------- */
 int rd_bn_stats_t(int32_t dtype, const void* x, int64_t M, int32_t C, int32_t ldx, float* stat_partial, int32_t* n_tiles, void* stream);
 int rd_bn_act_t(int32_t dtype, const void* x1, int32_t ldx1, const float* scale1, const float* shift1, const void* x2, int32_t ldx2, const float* scale2, const float* shift2, void* y, int32_t ldy, int64_t M, int32_t C, int32_t act, void* stream);

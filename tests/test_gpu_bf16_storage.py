@@ -1,9 +1,11 @@
 """bf16 STORAGE path (BASELINE.json configs 3 / 5): NHWC activations and their gradients live in HBM as bf16, convolutions run on
 v_mfma_f32_32x32x16_bf16 with fp32 accumulation, BatchNorm statistics / losses / parameters / parameter gradients / SGD stay fp32.
 
-Kernel level: every storage-typed entry point (`*_t` with RD_DTYPE_BF16) against a float64 torch evaluation of the SAME bf16 inputs;
-outputs are compared with the reference rounded to bf16 -- one bf16 ulp (2^-8 relative) is the bar, because a 1e-7 fp32
-summation-order difference can move a value across a rounding boundary.
+Kernel level: the storage-typed convolution and weight-gradient entry points (`*_t` with RD_DTYPE_BF16) against a float64 torch evaluation
+of the SAME bf16 inputs; outputs are compared with the reference rounded to bf16 -- one bf16 ulp (2^-8 relative) is the bar, because a
+1e-7 fp32 summation-order difference can move a value across a rounding boundary.  Of the BatchNorm / activation / stem-pool forms of
+csrc/norm_act.hip only three are launched here, at one shape (test_norm_kernels_bf16_storage); tests/test_gpu_norm_bf16.py holds every
+one of them to float64 with their rounding points, on channel windows, without an ulp slack.
 Step level: the CPU oracle with the same rounding points (tensors rounded where the HIP plan stores them, conv operands and
 gradients bf16, fp32 everywhere else), stated tolerances in each test."""
 import ctypes as C
