@@ -37,6 +37,12 @@ extern "C" {
 
 const char* rd_last_error(void);
 int rd_abi_version(void);
+/* The prototype of every entry point of this header, derived by the compiler (csrc/abi.cpp): entry i of rd_abi_entries() is
+ * "<name> <ret>:<args>" with one character per type -- p pointer, s char pointer, f float, d double, b h i l / B H I L signed /
+ * unsigned integer of 1, 2, 4, 8 bytes -- e.g. "rd_fill i:plfp"; NULL when i is out of range.  Bindings set their prototypes from
+ * it (radar_depth_amd/_lib.py). */
+int rd_abi_entries(void);
+const char* rd_abi_entry(int i);
 /* number of CUs / name of device 0 as the library sees it (diagnostics) */
 int rd_device_info(int* n_cu, char* name, int name_len);
 

@@ -61,6 +61,10 @@ class RadarDepthHipError(RuntimeError):
 
 
 _lib = None
+# type characters of the library's prototype table (rd_abi_entry, include/radar_depth_hip.h)
+_CTYPE = {"p": C.c_void_p, "s": C.c_char_p, "f": C.c_float, "d": C.c_double,
+          "b": C.c_int8, "h": C.c_int16, "i": C.c_int32, "l": C.c_int64,
+          "B": C.c_uint8, "H": C.c_uint16, "I": C.c_uint32, "L": C.c_uint64}
 
 
 def lib():
@@ -71,49 +75,19 @@ def lib():
             raise RadarDepthHipError(
                 "libradardepth_hip.so not built (%s). Run `python -m radar_depth_amd.build`; "
                 "there is no CPU fallback for the HIP path." % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        _lib.rd_last_error.restype = C.c_char_p
-        for name in ("rd_wgrad_workspace_floats", "rd_stem_wgrad_workspace_floats", "rd_smooth_workspace_floats",
-                     "rd_head_conv_bwd_workspace_floats", "rd_gconv_workspace_floats", "rd_wgrad_bf16_workspace_floats",
-                     "rd_wgrad_split_workspace_floats", "rd_stage_train_workspace_bytes", "rd_depth_metrics_frames_workspace_floats",
-                     "rd_lidar_sparsify_workspace_bytes", "rd_render_workspace_bytes", "rd_berhu_workspace_floats",
-                     "rd_depth_metrics_multidist_workspace_floats"):
-            if hasattr(_lib, name):
-                getattr(_lib, name).restype = C.c_int64
-        # on-device metric meters (csrc/loss_opt.hip): full prototypes, so that None / plain ints marshal as the C side expects
-        vp = C.c_void_p
-        for name, args in (("rd_masked_l1_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
-                           ("rd_masked_l2_sums_metrics", [vp, vp, C.c_int64, vp, vp, vp, vp]),
-                           # MaskedBerHuLoss (thresh travels as a double)
-                           ("rd_berhu_workspace_floats", [C.c_int64]),
-                           ("rd_masked_berhu_sums", [vp, vp, C.c_int64, C.c_double, vp, vp, vp]),
-                           ("rd_masked_berhu_sums_metrics", [vp, vp, C.c_int64, C.c_double, vp, vp, vp, vp]),
-                           ("rd_masked_berhu_bwd", [vp, vp, C.c_int64, vp, vp, vp, C.c_int32, vp]),
-                           ("rd_depth_metrics_frames_workspace_floats", [C.c_int32, C.c_int64]),
-                           ("rd_depth_metrics_frames", [vp, vp, C.c_int32, C.c_int64, vp, vp, vp]),
-                           ("rd_meter_update", [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
-                           # the distance-interval metrics (csrc/metrics_multidist.hip)
-                           ("rd_depth_metrics_multidist_workspace_floats", [C.c_int32, C.c_int64, C.c_int32]),
-                           ("rd_depth_metrics_multidist", [vp, vp, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]),
-                           ("rd_meter_update_multidist", [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp]),
-                           # the PnP-Depth kernels (csrc/pnp.hip)
-                           ("rd_act_gate_t", [C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, vp]),
-                           ("rd_pnp_update", [vp, C.c_int32, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp]),
-                           # the radar_filtered sparsifier (csrc/radar_filter.hip)
-                           ("rd_radar_filter_points", [vp] * 6 + [C.c_int32] * 3 + [vp] * 5),
-                           ("rd_radar_index_map", [vp, vp] + [C.c_int32] * 4 + [vp, vp]),
-                           ("rd_stage_index_filter_val", [vp] * 3 + [C.c_int32] * 9 + [vp] * 3),
-                           ("rd_stage_index_filter_train", [vp] * 3 + [C.c_int32] * 6 + [vp] * 3 + [C.c_int32] + [vp] * 3),
-                           # the lidar sparsifiers (csrc/lidar_sparsify.hip)
-                           ("rd_lidar_sparsify_workspace_bytes", [C.c_int32] * 3),
-                           ("rd_lidar_radar_sparsify", [vp, C.c_int64, vp, C.c_int64] + [C.c_int32] * 3 + [vp, vp, C.c_int64, vp]),
-                           ("rd_uniform_sparsify", [vp, C.c_int64] + [C.c_int32] * 3 + [C.c_int64, C.c_double, vp, C.c_uint64, C.c_uint64, vp, vp,
-                                                                                      C.c_int64, vp, vp]),
-                           # the comparison rows (csrc/visualize.hip)
-                           ("rd_render_workspace_bytes", [C.c_int32]),
-                           ("rd_render_rows", [vp, C.c_int64, vp, vp] + [C.c_int32] * 4 + [vp] * 4 + [C.c_int64, C.c_int64, vp])):
-            if hasattr(_lib, name):
-                getattr(_lib, name).argtypes = args
+        L = C.CDLL(LIB_PATH)
+        if not hasattr(L, "rd_abi_entry"):
+            raise RadarDepthHipError("%s has no prototype table (rd_abi_entries / rd_abi_entry): it was built before the binding "
+                                     "read its prototypes from the library; rebuild it" % LIB_PATH)
+        # every prototype comes from the table the compiler derived from include/radar_depth_hip.h (csrc/abi.cpp); this is the
+        # only one set by hand
+        L.rd_abi_entry.restype = C.c_char_p
+        for i in range(L.rd_abi_entries()):
+            name, sig = L.rd_abi_entry(i).decode().split(" ")
+            ret, args = sig.split(":")
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[a] for a in args]
+        _lib = L
     return _lib
 
 

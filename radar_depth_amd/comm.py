@@ -100,8 +100,7 @@ def allreduce_(tensor, stream, lo=0, hi=None):
     import torch
     hi = tensor.numel() if hi is None else hi
     dt = {torch.float32: RD_DTYPE_F32, torch.bfloat16: RD_DTYPE_BF16}[tensor.dtype]
-    check(lib().rd_allreduce_bucket(C.c_void_p(tensor.data_ptr() + lo * tensor.element_size()), C.c_int64(hi - lo), dt, stream),
-          "rd_allreduce_bucket")
+    check(lib().rd_allreduce_bucket(tensor.data_ptr() + lo * tensor.element_size(), hi - lo, dt, stream), "rd_allreduce_bucket")
 
 
 def broadcast_(tensor, stream, root=0):
@@ -109,9 +108,9 @@ def broadcast_(tensor, stream, root=0):
     dt = {torch.float32: RD_DTYPE_F32, torch.bfloat16: RD_DTYPE_BF16}.get(tensor.dtype)
     if dt is None:                       # e.g. the int64 num_batches_tracked counters: as raw fp32 words
         n_words = tensor.numel() * tensor.element_size() // 4
-        check(lib().rd_broadcast(C.c_void_p(tensor.data_ptr()), C.c_int64(n_words), RD_DTYPE_F32, root, stream), "rd_broadcast")
+        check(lib().rd_broadcast(tensor.data_ptr(), n_words, RD_DTYPE_F32, root, stream), "rd_broadcast")
         return
-    check(lib().rd_broadcast(C.c_void_p(tensor.data_ptr()), C.c_int64(tensor.numel()), dt, root, stream), "rd_broadcast")
+    check(lib().rd_broadcast(tensor.data_ptr(), tensor.numel(), dt, root, stream), "rd_broadcast")
 
 
 def destroy():

@@ -161,7 +161,7 @@ def stage_val_batch(image_u8, lidar_i16, radar_i16, crop_size=(450, 800), max_de
     md = float("inf") if max_depth < 0.0 else float(max_depth)
     inputs = torch.empty(B, 4, th, tw, dtype=torch.float32, device=image_u8.device)
     labels = torch.empty(B, 1, th, tw, dtype=torch.float32, device=image_u8.device)
-    check(lib().rd_stage_frames(ptr(image_u8), ptr(lidar_i16), ptr(radar_i16), B, H0, W0, i0, j0, th, tw, C.c_float(md),
+    check(lib().rd_stage_frames(ptr(image_u8), ptr(lidar_i16), ptr(radar_i16), B, H0, W0, i0, j0, th, tw, md,
                                 ptr(inputs), ptr(labels), current_stream()), "rd_stage_frames")
     index_map = None
     if apply or extras:
@@ -375,7 +375,7 @@ def stage_train_batch(image_u8, lidar_i16, radar_i16, params, crop_size=(450, 80
     work = torch.empty(max(int(L.rd_stage_train_workspace_bytes(B, H0, W0, ch, cw)), 16), dtype=torch.uint8, device=dev)
     base = prep.tables.data_ptr()
     check(L.rd_stage_frames_train(ptr(image_u8), ptr(lidar_i16), ptr(radar_i16), B, H0, W0, ch, cw, C.c_void_p(prep.records.ctypes.data),
-                                  *[C.c_void_p(base + 4 * o) for o in prep.offsets], ptr(work), C.c_float(md), 1 if modality == "rgb" else 0,
+                                  *[C.c_void_p(base + 4 * o) for o in prep.offsets], ptr(work), md, 1 if modality == "rgb" else 0,
                                   ptr(inputs), ptr(labels), current_stream()), "rd_stage_frames_train")
     index_map = None
     if apply or extras:

@@ -276,7 +276,7 @@ class LateFusionPlan:
         if pos < a.c0 + a.C and key not in ent:
             ent[key] = (here, id(lst))
             ent["prod"].append((C.c_void_p(0), a.c0, a.C))
-            self.op(lst, "split_pieces@%x+%d" % (a.t.data_ptr(), a.c0), self.L.rd_split_pieces, a.ptr, a.ld, C.c_int64(m), a.C, ptr_, ent["plane"], self.stream)
+            self.op(lst, "split_pieces@%x+%d" % (a.t.data_ptr(), a.c0), self.L.rd_split_pieces, a.ptr, a.ld, m, a.C, ptr_, ent["plane"], self.stream)
         elif key in ent and ent[key][0] != here:
             # a later consumer of the same stand-alone planes on ANOTHER stream: order it behind the stream the split pass was issued on
             # (the shipped models have no such consumer; a new one must not race the pass)
@@ -495,7 +495,7 @@ class LateFusionPlan:
     def _emit_pieces(self, q):
         """rd_gconv_split / rd_gconv_split_pre (input as piece planes) / rd_gemm_taps_split: three-piece weight operand."""
         pre = q.fam == "gconv_split_pre"
-        head = (C.byref(q.d), *(q.planes if pre else (q.x.ptr,)), _p(q.w), C.c_int64(q.k * q.k * q.x.C * q.out.C), q.out.ptr)
+        head = (C.byref(q.d), *(q.planes if pre else (q.x.ptr,)), _p(q.w), q.k * q.k * q.x.C * q.out.C, q.out.ptr)
         if q.bnb:
             self.op(q.lst, q.name, self.L.rd_gconv_split_pre_bnbwd if pre else self.L.rd_gconv_split_bnbwd, *head, *q.bnb, self.stream)
         else:
@@ -539,7 +539,6 @@ class LateFusionPlan:
     def _operand(self, fam, w0, taps, rows, cols, flip):
         """Packed weight operand of a launch of family fam -> (buffer, pack-job quad: 3 pieces / 2 bf16 / 1 fp32, None: Winograd's own job)."""
         if fam == "wino":
-            self.L.rd_wino_packed_bytes.restype = C.c_int64
             cout, cin = (cols, rows) if not flip else (rows, cols)
             u = self.buf(int(self.L.rd_wino_packed_bytes(cout, cin, flip)) // 2, dtype=torch.bfloat16)
             self.wino_jobs.append((w0, u, cout, cin, flip))
@@ -682,7 +681,7 @@ class LateFusionPlan:
                 self.persistent.append(dx.t)
                 self.persistent_zero_checks.append(_strided_zero_check(dx.t, dd))
             else:
-                self.op(self.bwd, name + ".zero", self.L.rd_fill, dx.ptr, C.c_int64(dx.t.numel() * dx.t.element_size() // 4), C.c_float(0.0),
+                self.op(self.bwd, name + ".zero", self.L.rd_fill, dx.ptr, dx.t.numel() * dx.t.element_size() // 4, C.c_float(0.0),
                         self.stream)
         fam = self._confirm_dgrad(ctx, dd, dout, dx, yplanes is not None, zero_fill)
         # The BatchNorm behind this convolution's forward input can take its backward sums from this launch's epilogue: rd_gconv_bnbwd on
@@ -795,7 +794,7 @@ class LateFusionPlan:
         Cc = bn.weight.shape[0]
         co = dict(name=name, bn=bn, C=Cc, count=count, mean=self.buf(Cc), invstd=self.buf(Cc), scale=self.buf(Cc), shift=self.buf(Cc))
         if self.train:
-            self.op(lst, name + ".finalize", self.L.rd_bn_finalize, _p(stat), tiles, ld, c0, Cc, C.c_int64(count), _p(bn.weight),
+            self.op(lst, name + ".finalize", self.L.rd_bn_finalize, _p(stat), tiles, ld, c0, Cc, count, _p(bn.weight),
                     _p(bn.bias), C.c_float(BN_EPS), C.c_float(BN_MOMENTUM), _p(bn.running_mean), _p(bn.running_var),
                     _p(bn.num_batches_tracked), _p(co["mean"]), _p(co["invstd"]), _p(co["scale"]), _p(co["shift"]), self.stream)
         else:
@@ -809,7 +808,7 @@ class LateFusionPlan:
             out = self.act(x1.N, x1.H, x1.W, x1.C)
         c2 = co2 or {}      # (an identity residual has no coefficients: NULL)
         self.op_pieces(self.fwd, name, "rd_bn_act", [out], x1.ptr, x1.ld, _p(co1["scale"]), _p(co1["shift"]), *self._addend(x2),
-                       _p(c2.get("scale")), _p(c2.get("shift")), out.ptr, out.ld, C.c_int64(x1.M), x1.C, act)
+                       _p(c2.get("scale")), _p(c2.get("shift")), out.ptr, out.ld, x1.M, x1.C, act)
         self.taps[name] = out
         return out
 
@@ -832,13 +831,13 @@ class LateFusionPlan:
             dx1 = self.act(x1.N, x1.H, x1.W, Cc)
             self._bn_apply_x(name + ".bn1", dy, x1, red, tiles, co1, act, dx1)
             return dx1, None
-        tiles = self.L.rd_bn_bwd_tiles(C.c_int64(M), Cc)
+        tiles = self.L.rd_bn_bwd_tiles(M, Cc)
         red = self.buf(tiles, 3, Cc)
         if lone and x2 is None and act != ACT_NONE:
             # lone act(bn(x1)): the activation's sign is recomputed from x1 in both passes -- y is not read and the masked
             # gradient is never materialised
             self.op(self.bwd, name + ".bwd_reduce", self.L.rd_bn_bwd_reduce_x_t, self.dt, dy.ptr, dy.ld, x1.ptr, x1.ld, _p(co1["mean"]),
-                    _p(co1["scale"]), _p(co1["shift"]), C.c_void_p(0), 0, C.c_int64(M), Cc, act, _p(red), self.stream)
+                    _p(co1["scale"]), _p(co1["shift"]), C.c_void_p(0), 0, M, Cc, act, _p(red), self.stream)
             dx1 = self.act(x1.N, x1.H, x1.W, Cc)
             self._bn_apply_x(name + ".bn1", dy, x1, red, tiles, co1, act, dx1)
             return dx1, None
@@ -846,7 +845,7 @@ class LateFusionPlan:
             # act(bn1(x1) + bn2(x2)): same idea for both operands at once (y not read, g not materialised, dy read once per pass)
             self.op(self.bwd, name + ".bwd_reduce", self.L.rd_bn_bwd_reduce_x2_t, self.dt, dy.ptr, dy.ld, x1.ptr, x1.ld, _p(co1["mean"]),
                     _p(co1["scale"]), _p(co1["shift"]), x2.ptr, x2.ld, _p(co2["mean"]), _p(co2["scale"]), _p(co2["shift"]),
-                    C.c_int64(M), Cc, act, _p(red), self.stream)
+                    M, Cc, act, _p(red), self.stream)
             dx1 = self.act(x1.N, x1.H, x1.W, Cc)
             if dx2 is None:
                 dx2 = self.act(x2.N, x2.H, x2.W, Cc)
@@ -856,13 +855,13 @@ class LateFusionPlan:
                            _p(b1.weight), _p(co1["mean"]), _p(co1["invstd"]), _p(co1["scale"]), _p(co1["shift"]),
                            _p(b2.weight), _p(co2["mean"]), _p(co2["invstd"]), _p(co2["scale"]), _p(co2["shift"]), act,
                            _p(self.grad_of(b1.weight)), _p(self.grad_of(b1.bias)), _p(self.grad_of(b2.weight)), _p(self.grad_of(b2.bias)),
-                           _p(coef), dx1.ptr, dx1.ld, dx2.ptr, dx2.ld, C.c_int64(M), Cc)
+                           _p(coef), dx1.ptr, dx1.ld, dx2.ptr, dx2.ld, M, Cc)
             return dx1, dx2
         # with no activation g == dy: skip the copy and let the apply pass read dy directly
         g = self.act(x1.N, x1.H, x1.W, Cc) if act != ACT_NONE else dy
         self.op(self.bwd, name + ".bwd_reduce", self.L.rd_bn_bwd_reduce_t, self.dt, dy.ptr, dy.ld, *self._addend(y), x1.ptr, x1.ld, _p(co1["mean"]),
                 *self._addend(x2 if co2 else None), _p((co2 or {}).get("mean")), g.ptr if act != ACT_NONE else C.c_void_p(0), g.ld,
-                C.c_int64(M), Cc, act, _p(red), self.stream)
+                M, Cc, act, _p(red), self.stream)
         dx1 = self.act(x1.N, x1.H, x1.W, Cc)
         self._bn_apply(name + ".bn1", g, x1, red, tiles, 1, co1, dx1)
         if co2 is not None:
@@ -877,14 +876,14 @@ class LateFusionPlan:
         coef = self.buf(3 * co["C"])
         self.op_pieces(self.bwd, name + ".bwd_apply", "rd_bn_bwd_apply", [dx], g.ptr, g.ld, x.ptr, x.ld, _p(red), tiles, which,
                        _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)),
-                       _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"])
+                       _p(coef), dx.ptr, dx.ld, x.M, co["C"])
 
     def _bn_apply_x(self, name, dy, x, red, tiles, co, act, dx):
         bn = co["bn"]
         coef = self.buf(3 * co["C"])
         self.op_pieces(self.bwd, name + ".bwd_apply", "rd_bn_bwd_apply_x", [dx], dy.ptr, dy.ld, x.ptr, x.ld, _p(red), tiles,
                        _p(bn.weight), _p(co["mean"]), _p(co["invstd"]), _p(co["scale"]), _p(co["shift"]), act,
-                       _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)), _p(coef), dx.ptr, dx.ld, C.c_int64(x.M), co["C"])
+                       _p(self.grad_of(bn.weight)), _p(self.grad_of(bn.bias)), _p(coef), dx.ptr, dx.ld, x.M, co["C"])
 
     # ------------------------------------------------------------------ network pieces
     def _stem(self, name, planes, strides, conv, bn, act, out_name):
@@ -1059,10 +1058,10 @@ class LateFusionPlan:
         if self.bnb_out is not None:
             red, tiles = self.bnb_out
         else:
-            M, tiles = R.M, self.L.rd_bn_bwd_tiles(C.c_int64(R.M), half)
+            M, tiles = R.M, self.L.rd_bn_bwd_tiles(R.M, half)
             red = self.buf(tiles, 3, half)
             self.op(self.bwd, name + ".bn1.bwd_reduce", self.L.rd_bn_bwd_reduce_x_t, self.dt, dy1.ptr, dy1.ld, x1.ptr, x1.ld, _p(co["mean"]),
-                    _p(co["scale"]), _p(co["shift"]), C.c_void_p(0), 0, C.c_int64(M), half, ACT_RELU, _p(red), self.stream)
+                    _p(co["scale"]), _p(co["shift"]), C.c_void_p(0), 0, M, half, ACT_RELU, _p(red), self.stream)
         self._bn_apply_x(name + ".bn1", dy1, x1, red, tiles, co, ACT_RELU, dR.chan(0, half))
         dx = self.conv_bwd(ctx["cR"], dR)
         self.taps["grad_out:" + name] = dy
@@ -1233,7 +1232,7 @@ class LateFusionPlan:
     def _gate(self, name, dy, y, out):
         """out = dy * [y > 0]: the backward of a ReLU, gated by the activation the eval forward keeps."""
         assert dy.M == y.M == out.M and dy.C == y.C == out.C
-        self.op(self.pnp_bwd, name, self.L.rd_act_gate_t, self.dt, dy.ptr, dy.ld, y.ptr, y.ld, out.ptr, out.ld, C.c_int64(y.M), y.C, ACT_RELU,
+        self.op(self.pnp_bwd, name, self.L.rd_act_gate_t, self.dt, dy.ptr, dy.ld, y.ptr, y.ld, out.ptr, out.ld, y.M, y.C, ACT_RELU,
                 self.stream)
         return out
 

@@ -2,8 +2,6 @@
 MaskedL1Loss (:44-54), MaskedMSELoss (:31-41), MaskedBerHuLoss (:57-81) and SmoothnessLoss (:8-28) as HIP reductions behind
 torch.autograd.  Same call signatures; losses are 0-dim CUDA tensors; an all-invalid target gives NaN exactly like the reference
 (MaskedBerHuLoss: NaN where the reference raises)."""
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
@@ -23,10 +21,10 @@ class _MaskedL1Fn(torch.autograd.Function):
         pred = pred.contiguous()
         target = target.contiguous()
         n = pred.numel()
-        tiles = L.rd_loss_tiles(C.c_int64(n))
+        tiles = L.rd_loss_tiles(n)
         ws = _f64(2 * tiles, pred.device)
         sums = _f64(2, pred.device)
-        check(getattr(L, cls.SUMS)(ptr(pred), ptr(target), C.c_int64(n), ptr(ws), ptr(sums), current_stream()), cls.SUMS)
+        check(getattr(L, cls.SUMS)(ptr(pred), ptr(target), n, ptr(ws), ptr(sums), current_stream()), cls.SUMS)
         ctx.save_for_backward(pred, target, sums)
         return (sums[0] / sums[1]).float()
 
@@ -35,7 +33,7 @@ class _MaskedL1Fn(torch.autograd.Function):
         pred, target, sums = ctx.saved_tensors
         dpred = torch.empty_like(pred)
         coef = gout.reshape(1).float().contiguous()
-        check(getattr(lib(), cls.BWD)(ptr(pred), ptr(target), C.c_int64(pred.numel()), ptr(sums), ptr(coef), ptr(dpred), 0,
+        check(getattr(lib(), cls.BWD)(ptr(pred), ptr(target), pred.numel(), ptr(sums), ptr(coef), ptr(dpred), 0,
                                       current_stream()), cls.BWD)
         return dpred, None
 

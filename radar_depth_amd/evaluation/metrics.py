@@ -41,10 +41,10 @@ class Result(object):
         output = output.contiguous().float()
         target = target.contiguous().float()
         n = output.numel()
-        tiles = L.rd_loss_tiles(C.c_int64(n))
+        tiles = L.rd_loss_tiles(n)
         ws = torch.empty(10 * tiles, dtype=torch.float64, device=output.device)
         sums = torch.empty(10, dtype=torch.float64, device=output.device)
-        check(L.rd_depth_metrics(ptr(output), ptr(target), C.c_int64(n), ptr(ws), ptr(sums), current_stream()), "rd_depth_metrics")
+        check(L.rd_depth_metrics(ptr(output), ptr(target), n, ptr(ws), ptr(sums), current_stream()), "rd_depth_metrics")
         s = sums.cpu().numpy()          # the only host synchronisation
         cnt = s[0]
         mean = (lambda v: float(v / cnt)) if cnt > 0 else (lambda v: float("nan"))
@@ -180,7 +180,7 @@ class DeviceAverageMeter(object):
         key = (frames, hw, per_frame)
         if key not in self._ws:
             nd = (int(L.rd_depth_metrics_frames_workspace_floats(frames, hw)) // 2 if per_frame else
-                  10 * L.rd_loss_tiles(C.c_int64(hw)))
+                  10 * L.rd_loss_tiles(hw))
             self._ws[key] = (torch.empty(nd, dtype=torch.float64, device=self.device),
                              torch.empty(frames, 10, dtype=torch.float64, device=self.device))
         ws, sums = self._ws[key]
@@ -189,7 +189,7 @@ class DeviceAverageMeter(object):
             check(L.rd_depth_metrics_frames(ptr(pred), ptr(target), frames, hw, ptr(ws), ptr(sums), s), "rd_depth_metrics_frames")
             weights = None
         else:
-            check(L.rd_depth_metrics(ptr(pred), ptr(target), C.c_int64(hw), ptr(ws), ptr(sums), s), "rd_depth_metrics")
+            check(L.rd_depth_metrics(ptr(pred), ptr(target), hw, ptr(ws), ptr(sums), s), "rd_depth_metrics")
             weights = self._weight(pred.size(0) if n is None else n)
         check(L.rd_meter_update(ptr(sums), frames, ptr(weights), ptr(masks), self.groups, ptr(self.buf), ptr(self.last_buf), s),
               "rd_meter_update")
@@ -362,7 +362,7 @@ class DeviceAverageMeter_multidist(DeviceAverageMeter):
         self._alloc()
         L, ni = lib(), len(self.dist_interval)
         ws, sums = self._buffers(frames, hw)
-        return [(tag + ".multidist", L.rd_depth_metrics_multidist, (ptr(pred), ptr(target), frames, C.c_int64(hw), self._edges, ni, ptr(ws),
+        return [(tag + ".multidist", L.rd_depth_metrics_multidist, (ptr(pred), ptr(target), frames, hw, self._edges, ni, ptr(ws),
                                                                      ptr(sums), stream)),
                 (tag + ".meter_multidist", L.rd_meter_update_multidist, (ptr(sums), frames, ni, ptr(weights), ptr(masks), self.groups,
                                                                          ptr(self._buf), ptr(self._last_buf), ptr(self._valid_buf), stream))]

@@ -234,7 +234,7 @@ class HipTrainStep:
         p = self.plan
         self.n_out = batch * p.Ho * p.Wo
         self.target = torch.zeros(batch, 1, p.Ho, p.Wo, device=dev)
-        tiles = self.L.rd_loss_tiles(C.c_int64(self.n_out))
+        tiles = self.L.rd_loss_tiles(self.n_out)
         self.l1_ws = torch.zeros(2 * tiles, dtype=torch.float64, device=dev)
         if criterion == "berhu":                              # one workspace serves the plain call and the one with the metric sums
             nfl = int(self.L.rd_berhu_workspace_floats(self.n_out))
@@ -383,18 +383,18 @@ class HipTrainStep:
     def _l1_ops(self, tag, pred, sums, s):
         if self.metrics:
             msums, meter = self._meter_of[id(pred)]
-            ops = [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
+            ops = [(tag + ".sums_metrics", self._f_sums_metrics, (ptr(pred), ptr(self.target), self.n_out) + self._sums_extra +
                     (ptr(self.metrics_ws), ptr(sums), ptr(msums), s)),
                    (tag + ".meter", self.L.rd_meter_update, (ptr(msums), 1, ptr(self._meter_weight), None, 1, ptr(meter.buf),
                                                              ptr(meter.last_buf), s))]
             if self.meter_multidist is not None:        # the same Result per distance interval: one binning pass, one update
                 ops += self._multidist_of[id(pred)].update_ops(tag, pred, self.target, 1, self.n_out, self._meter_weight, None, s)
             return ops
-        return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), C.c_int64(self.n_out)) + self._sums_extra +
+        return [(tag + ".sums", self._f_sums, (ptr(pred), ptr(self.target), self.n_out) + self._sums_extra +
                  (ptr(self.l1_ws), ptr(sums), s))]
 
     def _l1_bwd_ops(self, tag, pred, sums, coef, dpred, accumulate, s):
-        return [(tag + ".bwd", self._f_bwd, (ptr(pred), ptr(self.target), C.c_int64(self.n_out), ptr(sums), coef, ptr(dpred), accumulate, s))]
+        return [(tag + ".bwd", self._f_bwd, (ptr(pred), ptr(self.target), self.n_out, ptr(sums), coef, ptr(dpred), accumulate, s))]
 
     def _latefusion_pieces(self):
         p = self.plan
@@ -431,7 +431,7 @@ class HipTrainStep:
 
     def _sgd_ops(self):
         st = self.st
-        return [("sgd_step", self.L.rd_sgd_step, (ptr(st["arena"]), ptr(st["grads"]), ptr(st["mom"]), C.c_int64(st["total"]), C.c_float(self.lr),
+        return [("sgd_step", self.L.rd_sgd_step, (ptr(st["arena"]), ptr(st["grads"]), ptr(st["mom"]), st["total"], C.c_float(self.lr),
                                                    C.c_float(self.momentum), C.c_float(self.wd), C.c_float(1.0 / self.world), 0,
                                                    self.plan.streams[0]))]
 
@@ -443,7 +443,7 @@ class HipTrainStep:
                ("bucket%d.wait" % i, self.L.rd_stream_wait_event, (cs, self._bucket_events[i]))]
         ops += [("bucket%d.wait_side" % i, self.L.rd_stream_wait_event, (cs, ev)) for ev in self._bucket_side_events[i]]
         g = self.st["grads"]
-        ops += [("bucket%d.allreduce" % i, self.L.rd_allreduce_bucket, (C.c_void_p(g.data_ptr() + 4 * lo), C.c_int64(hi - lo), 0, cs))
+        ops += [("bucket%d.allreduce" % i, self.L.rd_allreduce_bucket, (C.c_void_p(g.data_ptr() + 4 * lo), hi - lo, 0, cs))
                 for lo, hi in self._buckets[i]]
         return ops
 
@@ -522,7 +522,7 @@ class HipTrainStep:
         if want != self._bound:
             for i, k, a, which in self._bind_sites:
                 a.value = want[which]                                             # (the Python-loop diagnostics path reads the argument objects)
-                check(self.L.rd_optable_set_word(self._table.h, i, k, C.c_uint64(want[which])), "rd_optable_set_word")
+                check(self.L.rd_optable_set_word(self._table.h, i, k, want[which]), "rd_optable_set_word")
             self._bound = want
         for pl in self.plans:                                   # (plan state, shared with the eager forward of a cached plan: checked every step)
             if pl._x_bound != want[0]:
@@ -737,7 +737,7 @@ class HipPnPInference:
         self.sparse = torch.zeros(batch, 1, p.Ho, p.Wo, device=dev)          # contiguous copy of the sparse plane
         self._alpha = float(alpha)
         self.alpha_dev = torch.full((1,), float(alpha), device=dev)
-        tiles = self.L.rd_loss_tiles(C.c_int64(self.n_out))
+        tiles = self.L.rd_loss_tiles(self.n_out)
         self._ws = torch.zeros(2 * tiles, dtype=torch.float64, device=dev)
         self._sums = torch.zeros(self.iters, 2, dtype=torch.float64, device=dev)
         self._coef = torch.zeros(1, device=dev)
@@ -755,7 +755,7 @@ class HipPnPInference:
 
     # ---- the loop as one op list: prep, fwd (front | rear), then per step k: grad_k, update, rear; a spare grad behind the end
     def _grad_ops(self, k):
-        p, s, L, n = self.plan, self.plan.streams[0], self.L, C.c_int64(self.n_out)
+        p, s, L, n = self.plan, self.plan.streams[0], self.L, self.n_out
         sums = C.c_void_p(self._sums.data_ptr() + 16 * k)
         loss = C.c_void_p(self._loss_all.data_ptr() + 4 * k)
         f_sums, f_bwd = [getattr(L, "rd_masked_%s_%s" % (self.criterion, q)) for q in ("sums", "bwd")]
@@ -765,7 +765,7 @@ class HipPnPInference:
 
     def _update_ops(self):
         z, g = self.plan.pnp_z, self.plan.pnp_g
-        return [("pnp.update", self.L.rd_pnp_update, (z.ptr, z.ld, g.ptr, g.ld, C.c_int64(z.M), z.C, ptr(self.alpha_dev), self.plan.streams[0]))]
+        return [("pnp.update", self.L.rd_pnp_update, (z.ptr, z.ld, g.ptr, g.ld, z.M, z.C, ptr(self.alpha_dev), self.plan.streams[0]))]
 
     def _build_table(self):
         from .optable import OpTable

@@ -48,7 +48,7 @@ class Filter_layer(_PlanOnly):
         n, c, h, w = sparse.shape
         assert c == 1 and dense.shape == sparse.shape
         kept, mask = torch.empty_like(sparse), torch.empty_like(sparse)
-        check(lib().rd_radar_filter(ptr(sparse), n, 1, 0, C.c_int64(h * w), ptr(dense), ptr(kept), ptr(mask),
+        check(lib().rd_radar_filter(ptr(sparse), n, 1, 0, h * w, ptr(dense), ptr(kept), ptr(mask),
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "rd_radar_filter")
         return kept, mask
 
@@ -131,7 +131,7 @@ class MultistagePlan:
         """The radar filter between the stages as a plan op (name, C-ABI function, arguments) on stage 1's main stream."""
         p1 = self.p1
         hw = p1.H * p1.W
-        return ("radar_filter", self.L.rd_radar_filter, (ptr(p1.x_in), p1.N, p1.x_in.shape[1], 3, C.c_int64(hw), ptr(p1.pred), ptr(self.kept),
+        return ("radar_filter", self.L.rd_radar_filter, (ptr(p1.x_in), p1.N, p1.x_in.shape[1], 3, hw, ptr(p1.pred), ptr(self.kept),
                                                          ptr(self.mask), p1.streams[0]))
 
     def filter_op(self):

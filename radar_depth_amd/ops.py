@@ -72,7 +72,7 @@ def gconv_split(desc, x, w_split, out, bias=None, act=0, act_cols=0, addend=None
     """fp32 convolution rebuilt from six bf16 MFMAs per product (three-piece operands): rd_gconv_split."""
     _poison()
     assert w_split.dtype == torch.bfloat16 and w_split.shape[0] == 3
-    check(lib().rd_gconv_split(C.byref(desc), ptr(_f32(x)), ptr(w_split), C.c_int64(w_split[0].numel()), ptr(_f32(out)), ptr(bias), act,
+    check(lib().rd_gconv_split(C.byref(desc), ptr(_f32(x)), ptr(w_split), w_split[0].numel(), ptr(_f32(out)), ptr(bias), act,
                                act_cols, ptr(addend), ld_add, ptr(stat), current_stream()), "rd_gconv_split")
     return out
 
@@ -92,7 +92,7 @@ def gemm_taps_split(desc, x, w_split, out, bias=None, act=0, act_cols=0, addend=
     """rd_gconv_split's contract for descriptors whose phases have 1..4 taps, on the channel-grouped kernel (csrc/gemm_taps_split.hip)."""
     _poison()
     assert w_split.dtype == torch.bfloat16 and w_split.shape[0] == 3
-    check(lib().rd_gemm_taps_split(C.byref(desc), ptr(_f32(x)), ptr(w_split), C.c_int64(w_split[0].numel()), ptr(_f32(out)), ptr(bias), act,
+    check(lib().rd_gemm_taps_split(C.byref(desc), ptr(_f32(x)), ptr(w_split), w_split[0].numel(), ptr(_f32(out)), ptr(bias), act,
                                    act_cols, ptr(addend), ld_add, ptr(stat), current_stream()), "rd_gemm_taps_split")
     return out
 
@@ -108,7 +108,7 @@ def split_pieces(x_nhwc):
         x_nhwc.stride(3) == 1 and x_nhwc.stride(1) == w * ld and x_nhwc.stride(0) == h * w * ld)), \
         "expected an NHWC CUDA float32 tensor (a channel slice of a wider buffer is fine)"
     pc = torch.empty(3, c // 16, m, 16, dtype=torch.bfloat16, device=x_nhwc.device)
-    check(lib().rd_split_pieces(ptr(x_nhwc), ld, C.c_int64(m), c, ptr(pc), C.c_int64(pc[0].numel()), current_stream()), "rd_split_pieces")
+    check(lib().rd_split_pieces(ptr(x_nhwc), ld, m, c, ptr(pc), pc[0].numel(), current_stream()), "rd_split_pieces")
     return pc
 
 
@@ -121,7 +121,7 @@ def gconv_split_pre(desc, x_pieces, w_split, out, bias=None, act=0, act_cols=0, 
     import torch
     _poison()
     assert x_pieces.dtype == torch.bfloat16 and x_pieces.shape[0] == 3 and w_split.dtype == torch.bfloat16 and w_split.shape[0] == 3
-    check(lib().rd_gconv_split_pre(C.byref(desc), ptr(x_pieces), C.c_int64(x_pieces[0].numel()), ptr(w_split), C.c_int64(w_split[0].numel()),
+    check(lib().rd_gconv_split_pre(C.byref(desc), ptr(x_pieces), x_pieces[0].numel(), ptr(w_split), w_split[0].numel(),
                                    ptr(_f32(out)), ptr(bias), act, act_cols, ptr(addend), ld_add, ptr(stat), current_stream()), "rd_gconv_split_pre")
     return out
 
@@ -197,7 +197,7 @@ def gconv_bnbwd(desc, dout, w_packed, dx, bn_x, ld_x, mean, scale, shift, act, r
 
 
 def fill(t, v):
-    check(lib().rd_fill(ptr(t), C.c_int64(t.numel()), C.c_float(v), current_stream()), "rd_fill")
+    check(lib().rd_fill(ptr(t), t.numel(), v, current_stream()), "rd_fill")
     return t
 
 
@@ -264,10 +264,10 @@ def wgrad_reduce_batched(jobs):
 def bn_stats(x2d, C_):
     """x2d: [M, ld] view (ld >= C_).  Returns (partial [tiles,2,C], tiles)."""
     M = x2d.shape[0]
-    tiles = lib().rd_bn_stats_tiles(C.c_int64(M))
+    tiles = lib().rd_bn_stats_tiles(M)
     part = torch.zeros(tiles, 2, C_, device=x2d.device)
     nt = C.c_int32(0)
-    check(lib().rd_bn_stats(ptr(x2d), C.c_int64(M), C_, x2d.stride(0), ptr(part), C.byref(nt), current_stream()), "rd_bn_stats")
+    check(lib().rd_bn_stats(ptr(x2d), M, C_, x2d.stride(0), ptr(part), C.byref(nt), current_stream()), "rd_bn_stats")
     assert nt.value == tiles
     return part, tiles
 
@@ -310,8 +310,8 @@ def wgrad_split_pre_supported(desc):
 def wgrad_split_pre(desc, x_pieces, dy_pieces, slabs):
     """rd_wgrad_split with both operands already split by their producers (ops.split_pieces)."""
     _poison()
-    check(lib().rd_wgrad_split_pre(C.byref(desc), ptr(x_pieces), C.c_int64(x_pieces[0].numel()), ptr(dy_pieces), C.c_int64(dy_pieces[0].numel()),
-                                   ptr(slabs), current_stream()), "rd_wgrad_split_pre")
+    check(lib().rd_wgrad_split_pre(C.byref(desc), ptr(x_pieces), x_pieces[0].numel(), ptr(dy_pieces), dy_pieces[0].numel(), ptr(slabs),
+                                   current_stream()), "rd_wgrad_split_pre")
 
 
 def wgrad_split_reduce(desc, slabs, grad, co_off=0, accumulate=False):
@@ -330,7 +330,6 @@ def wino_pack(w_oihw, flip=False):
     channels transposed, taps rotated by 180 degrees)."""
     o, i, kh, kw = w_oihw.shape
     assert kh == 3 and kw == 3
-    lib().rd_wino_packed_bytes.restype = C.c_int64
     nbytes = int(lib().rd_wino_packed_bytes(o, i, int(flip)))
     u = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w_oihw.device)
     check(lib().rd_wino_pack(ptr(_f32(w_oihw.contiguous())), o, i, int(flip), ptr(u), current_stream()), "rd_wino_pack")

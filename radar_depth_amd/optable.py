@@ -15,8 +15,14 @@ _BYREF = type(C.byref(C.c_int()))
 _M64 = (1 << 64) - 1
 
 
-def _word(a):
-    """ctypes argument -> 64-bit word exactly as the C prototype receives it."""
+def _word(a, ctype=None):
+    """ctypes argument -> 64-bit word exactly as the C prototype receives it.  ctype: the prototype's type of that argument (the
+    function's argtypes entry): a bare number is converted through it, a ctypes scalar of another type is refused."""
+    if ctype is not None:
+        if isinstance(a, C._SimpleCData) and type(a) is not ctype:
+            raise TypeError("a %s where the prototype takes a %s" % (type(a).__name__, ctype.__name__))
+        if isinstance(a, (int, float)):
+            a = ctype(a)
     if a is None:
         return 0
     if isinstance(a, bool):
@@ -29,13 +35,13 @@ def _word(a):
         return struct.unpack("<Q", struct.pack("<d", a.value))[0]
     if isinstance(a, C.c_void_p):
         return (a.value or 0) & _M64
-    if isinstance(a, (C.c_int64, C.c_int32, C.c_uint32, C.c_uint64, C.c_int16, C.c_int8)):
+    if isinstance(a, (C.c_int64, C.c_int32, C.c_uint32, C.c_uint64, C.c_int16, C.c_int8, C.c_uint16, C.c_uint8)):
         return a.value & _M64
     if isinstance(a, _BYREF):
         return C.addressof(a._obj)
     if isinstance(a, (C.Array, C.Structure)):
         return C.addressof(a)
-    raise TypeError("op-table: cannot marshal an argument of type %s" % type(a).__name__)
+    raise TypeError("cannot marshal an argument of type %s" % type(a).__name__)
 
 
 class OpTable:
@@ -55,10 +61,15 @@ class OpTable:
             words = (C.c_uint64 * max(n, 1))()
             slots = (C.c_int32 * max(n, 1))()
             stream_vals = {s.value for s in self.stream_objs if s.value}
+            proto = fn.argtypes
             for i, a in enumerate(args):
                 k = slot_of.get(id(a), -1) if isinstance(a, C.c_void_p) else -1
                 slots[i] = k
-                words[i] = 0 if k >= 0 else _word(a)
+                try:
+                    # (an argument beyond the prototype is counted and refused by rd_optable_add below)
+                    words[i] = 0 if k >= 0 else _word(a, proto[i] if i < len(proto) else None)
+                except TypeError as e:
+                    raise TypeError("op-table: %s (%s) argument %d: %s" % (name, fn.__name__, i, e)) from None
                 # a stream handed over as a FRESH c_void_p (equal value, different object) would be baked in and silently survive a
                 # later set_stream(): the last argument of every launching entry point is its stream -- it must be a slot
                 if k < 0 and i == n - 1 and isinstance(a, C.c_void_p) and a.value and a.value in stream_vals:

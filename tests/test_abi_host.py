@@ -26,6 +26,45 @@ def test_every_declared_symbol_is_exported(L):
     assert len(names) >= 45
     assert [n for n in names if not hasattr(L, n)] == []
     assert L.rd_abi_version() == 1
+    # the compiled prototype table (csrc/abi.cpp) names exactly the declared entry points, and lib() bound every one of them from it
+    table = dict(L.rd_abi_entry(i).decode().split(" ") for i in range(L.rd_abi_entries()))
+    assert sorted(table) == names and len(table) == L.rd_abi_entries()
+    assert L.rd_abi_entry(-1) is None and L.rd_abi_entry(L.rd_abi_entries()) is None
+    for n, sig in table.items():
+        assert len(getattr(L, n).argtypes) == len(sig.split(":")[1]), n
+    assert {n: table[n] for n in ("rd_fill", "rd_sgd_step", "rd_uniform_sparsify", "rd_wino_packed_bytes", "rd_last_error", "rd_loss_tiles",
+                                  "rd_optable_set_word")} == {
+        "rd_fill": "i:plfp", "rd_sgd_step": "i:ppplffffip", "rd_uniform_sparsify": "i:pliiildpLLpplpp", "rd_wino_packed_bytes": "l:iii",
+        "rd_last_error": "s:", "rd_loss_tiles": "i:l", "rd_optable_set_word": "i:piiL"}
+
+
+def test_arguments_travel_as_the_prototype_says(L):
+    """A bare number is converted through the compiled prototype (a 64-bit count is not cut to 32 bits), and a ctypes scalar of
+    another type than the prototype's is refused before the call."""
+    n = (1 << 33) + 5
+    assert L.rd_loss_tiles(n) == L.rd_loss_tiles(C.c_int64(n)) == 1024 and L.rd_loss_tiles(5) == 1
+    with pytest.raises(C.ArgumentError):
+        L.rd_fill(None, C.c_int32(1), 0.0, None)
+    with pytest.raises(C.ArgumentError):
+        L.rd_fill(None, 1, C.c_double(0.0), None)
+
+
+def test_no_prototype_is_set_outside_the_binding():
+    """Source lint: the prototypes come from the library's own table in radar_depth_amd/_lib.py; no other Python file assigns
+    .restype or .argtypes (each such line was a second copy of a prototype)."""
+    import glob
+    files = [os.path.join(REPO, "bench.py")]
+    for d in ("radar_depth_amd", "tools", "tests"):
+        files += glob.glob(os.path.join(REPO, d, "**", "*.py"), recursive=True)
+    assert len(files) > 30
+    offenders = []
+    for f in sorted(files):
+        if os.path.relpath(f, REPO) == os.path.join("radar_depth_amd", "_lib.py"):
+            continue
+        for n, line in enumerate(open(f), 1):
+            if re.search(r"\.(restype|argtypes)\s*=[^=]", line.split("#")[0]):
+                offenders.append("%s:%d" % (os.path.relpath(f, REPO), n))
+    assert offenders == []
 
 
 def test_argument_validation_without_gpu(L):

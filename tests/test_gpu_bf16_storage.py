@@ -189,7 +189,6 @@ def test_wgrad_bf16_storage(cfg):
         gy = _bf(torch.randn(n, co, d.Ho, d.Wo, generator=g))
         ref = torch.nn.grad.conv2d_weight(x.double(), (co, ci, k, k), gy.double(), s, k // 2)
     assert L.rd_wgrad_bf16_supported(C.byref(d)) == 1
-    L.rd_wgrad_bf16_workspace_floats.restype = C.c_int64
     slabs = torch.empty(int(L.rd_wgrad_bf16_workspace_floats(C.byref(d))), device="cuda")
     gw = torch.full((co, ci, k, k), float("nan"), device="cuda")
     xs, gys = _nhwc16(x), _nhwc16(gy)          # (named: a temporary would be freed -- and its block reused -- before the launch)

@@ -165,7 +165,6 @@ def test_gconv_launches_are_bitwise_reproducible():
         wp = torch.randn(9 * ci * co, device="cuda", generator=g)
         out = torch.zeros(n * h * w * co, device="cuda")
         stat = torch.zeros(L.rd_gconv_stat_tiles_ws(C.byref(d)) * 2 * co, device="cuda")
-        L.rd_gconv_workspace_floats.restype = C.c_int64
         nws = int(L.rd_gconv_workspace_floats(C.byref(d)))
         ws = torch.empty(max(nws, 1), device="cuda")
         ref = None

@@ -27,9 +27,7 @@ NAN = float("nan")
 
 def _lib():
     from radar_depth_amd._lib import lib
-    L = lib()
-    L.rd_gconv_workspace_floats.restype = C.c_int64
-    return L
+    return lib()
 
 
 def _p(t):

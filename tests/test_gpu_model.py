@@ -533,6 +533,23 @@ def test_op_table_replay_ranges_streams_and_errors():
     side.synchronize()
     assert bool((t[0] == 1.5).all()) and t[3].abs().max().item() == 0.0          # ops behind the failing one were not issued
     tb.close()
+    # bare numbers are marshalled through the compiled prototypes: the same bits as explicit wrappers (1027: not a multiple of a block)
+    n, got = 1027, []
+    torch.manual_seed(0)
+    p0, g0 = torch.randn(n, device="cuda"), torch.randn(n, device="cuda")
+    for wrap in (False, True):
+        i64, f32 = (C.c_int64, C.c_float) if wrap else (int, float)
+        p, g, mom, filled = p0.clone(), g0.clone(), torch.zeros(n, device="cuda"), torch.zeros(n + 5, device="cuda")
+        tb = OpTable(L, [("fill", L.rd_fill, (ptr(filled), i64(n), f32(2.5), s_main)),
+                         ("sgd", L.rd_sgd_step, (ptr(p), ptr(g), ptr(mom), i64(n), f32(0.01), f32(0.9), f32(1e-4), f32(0.5), 1, s_main))],
+                     [s_main])
+        tb.run()
+        side.synchronize()
+        tb.close()
+        got.append((filled, p, g, mom))
+    assert bool((got[0][0][:n] == 2.5).all()) and got[0][0][n:].abs().max().item() == 0.0 and not torch.equal(got[0][1], p0)
+    for a, b in zip(*got):
+        assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("storage,operands", [("fp32", None), ("bf16", None)])

@@ -145,7 +145,6 @@ def test_batched_pack_one_launch_every_layout_path_and_fold():
 # ------------------------------------------------------------------------------------------------ Winograd operands
 def test_wino_pack_single_and_batched_are_the_restatement():
     L = _L()
-    L.rd_wino_packed_bytes.restype = C.c_int64
     want = [PC.wino_expected(n) for n in range(len(PC.WINO))]
     ws = [_dev(PC.wino_weights(n)) for n in range(len(PC.WINO))]
     single = [_dev(np.full_like(e, PC.SENT16)) for e in want]

@@ -144,7 +144,6 @@ def test_stem_wgrad_split(cfg):
     hw = h * w
     planes = (C.c_void_p * 3)(*[x.data_ptr() + 4 * hw * (1 + c) if c < cin else None for c in range(3)])
     strides = (C.c_int64 * 3)(*[(cin + 1) * hw if c < cin else 0 for c in range(3)])
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     nws = int(L.rd_stem_wgrad_workspace_floats(n, h, w, cin, cout))
     want = torch.nn.grad.conv2d_weight(x[:, 1:].double(), (cout, cin, 7, 7), dout.double().permute(0, 3, 1, 2).contiguous(), stride=2, padding=3).cpu()
     err = {}
@@ -194,7 +193,6 @@ def test_stem_wgrad_split_bn_same_bits_as_two_passes(cfg):
     hw = h * w
     planes = (C.c_void_p * 3)(*[x_in.data_ptr() + 4 * hw * c if c < cin else None for c in range(3)])
     strides = (C.c_int64 * 3)(*[cin * hw if c < cin else 0 for c in range(3)])
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     nws = L.rd_stem_wgrad_workspace_floats(n, h, w, cin, cout)
     res = []
     for fused in (0, 1):

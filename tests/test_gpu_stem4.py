@@ -120,7 +120,6 @@ def test_stem4_wgrad(cfg):
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     dout = (torch.randn(n, ho, wo, cout, generator=gen) * torch.exp2(torch.randint(-6, 7, (1, 1, 1, cout), generator=gen).float())).cuda()
     planes, strides = _tables(x, cin, h, w)
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     nws = int(L.rd_stem_wgrad_workspace_floats(n, h, w, cin, cout))
     want = torch.nn.grad.conv2d_weight(x[:, 1:].double(), (cout, cin, 7, 7), dout.double().permute(0, 3, 1, 2).contiguous(), stride=2, padding=3).cpu()
     err = {}
@@ -158,7 +157,6 @@ def test_stem4_wgrad_split_bn_same_bits_as_two_passes(cfg):
     check(L.rd_bn_bwd_reduce_t(0, ptr(g), cout, None, 0, ptr(raw), cout, ptr(mean), None, 0, None, None, 0, C.c_int64(m), cout, 0, ptr(red),
                                current_stream()), "rd_bn_bwd_reduce_t")
     planes, strides = _tables(x_in, cin, h, w, first=0)
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     nws = L.rd_stem_wgrad_workspace_floats(n, h, w, cin, cout)
     res = []
     for fused in (0, 1):
@@ -195,7 +193,6 @@ def test_stem_five_planes_is_an_error():
     out = torch.full((n, ho, wo, cout), float("nan"), device="cuda")
     dout = torch.zeros(n, ho, wo, cout, device="cuda")
     gw = torch.full((cout, cin, 7, 7), float("nan"), device="cuda")
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     ws = torch.zeros(int(L.rd_stem_wgrad_workspace_floats(n, h, w, cin, cout)), device="cuda")
     assert L.rd_stem_fwd(planes, strides, cin, n, h, w, ptr(wp), cout, ptr(out), None, current_stream()) != 0
     assert L.rd_stem_fwd_split(planes, strides, cin, n, h, w, ptr(wp), cout, ptr(out), None, current_stream()) != 0

@@ -243,6 +243,13 @@ def test_op_table_marshals_every_plan_op():
     assert _word(C.c_float(1.0)) == 0x3F800000 and _word(-1) == 2 ** 64 - 1
     d = C.c_int32(5)
     assert _word(C.byref(d)) == C.addressof(d)
+    # given the prototype's type, a bare number becomes the bit pattern the C side receives ...
+    assert _word(1.0, C.c_float) == 0x3F800000 and _word(1.0, C.c_double) == 0x3FF0000000000000 and _word(-1, C.c_int64) == 2 ** 64 - 1
+    # ... and a wrapper of another type is refused (rd_fill's value is a float), naming the op, the entry point and the argument
+    s = C.c_void_p(0)
+    with pytest.raises(TypeError, match=r"x \(rd_fill\) argument 2"):
+        OpTable(L, [("x", L.rd_fill, (C.c_void_p(0), 1, C.c_double(0.0), s))], [s])
+    OpTable(L, [("x", L.rd_fill, (C.c_void_p(0), 1, 0.0, s))], [s]).close()
     with pytest.raises(RadarDepthHipError):
         OpTable(L, [("bad", L.rd_last_error, ())], [])                     # not a replayable entry point
     with pytest.raises(RadarDepthHipError):

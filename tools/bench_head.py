@@ -1,11 +1,10 @@
 """Timing of the head kernels (conv3 16 -> 1 forward / backward, bilinear) at the bench geometry: python tools/bench_head.py"""
-import ctypes as C, sys
+import sys
 import torch
 sys.path.insert(0, ".")
 from radar_depth_amd._lib import check, current_stream, lib, ptr
 from tools.bench_ops import timeit
 L = lib()
-L.rd_head_conv_bwd_workspace_floats.restype = C.c_int64
 N, H, W, Cc, Ho, Wo = 16, 240, 400, 16, 450, 800
 x = torch.randn(N, H, W, Cc, device="cuda")
 w = torch.randn(1, Cc, 3, 3, device="cuda")

@@ -19,7 +19,6 @@ for cin, cout, first in ((3, 64, 0), (1, 16, 3)):
     t = timeit(lambda: check(L.rd_stem_fwd(planes, strides, cin, N, H, W, ptr(wp), cout, ptr(out), ptr(stat), current_stream()), "stem_fwd"))
     gf = 2.0 * N * Ho * Wo * cout * 49 * cin / 1e9
     print("stem fwd  %d->%d: %7.1f us  %5.1f TF (%4.1f%% of fp32 peak)" % (cin, cout, t * 1e6, gf / t / 1e3, 100 * gf / t / 1e3 / 157.3))
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     ws = torch.empty(int(L.rd_stem_wgrad_workspace_floats(N, H, W, cin, cout)), device="cuda")
     gw = torch.empty(cout, cin, 7, 7, device="cuda")
     dout = torch.randn(N, Ho, Wo, cout, device="cuda")

@@ -27,7 +27,6 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     a = ap.parse_args()
     L = lib()
-    L.rd_stem_wgrad_workspace_floats.restype = C.c_int64
     n, cout, h, w = 16, 64, 450, 800
     hw = h * w
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1

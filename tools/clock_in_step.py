@@ -1,6 +1,6 @@
 """Effective shader clock while the training step runs continuously: RD_GCONV_TRACE=1 stamps every gconv workgroup with the cycle
 counter and the 100 MHz real-time counter; after N steps the buffer holds the last gconv launch of the step."""
-import ctypes as C, os, sys, types
+import os, sys, types
 import numpy as np, torch
 os.environ["RD_GCONV_TRACE"] = "1"
 sys.path.insert(0, ".")
@@ -17,7 +17,6 @@ torch.cuda.synchronize()
 L = lib()
 nwg = 256
 buf = np.zeros((nwg, 64), dtype=np.uint64)
-L.rd_gconv_trace_read.argtypes = [C.c_void_p, C.c_int]
 assert L.rd_gconv_trace_read(buf.ctypes.data, nwg) == 0
 n = int(buf[0, 0])
 cyc = (buf[:, n] - buf[:, 1]).astype(np.float64)

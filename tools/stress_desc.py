@@ -17,15 +17,12 @@ OPERANDS, STORAGE = ("bf16" if MODE != "fp32" else "fp32"), ("bf16" if MODE == "
 IO16 = 1 if STORAGE == "bf16" else 0
 adt = torch.bfloat16 if IO16 else torch.float32
 L = lib()
-L.rd_gconv_workspace_floats.restype = C.c_int64
 args = types.SimpleNamespace(arch=arch, decoder="upproj", modality="rgbd", pretrained=False)
 torch.manual_seed(0)
 made = create_model(args, [h, w])
 m, lw = made if isinstance(made, tuple) else (made, None)
 procedural_fill_(m)
 ts = HipTrainStep(m.cuda(), b, h, w, loss_weights=lw, operands=OPERANDS, storage=STORAGE)
-L.rd_wgrad_workspace_floats.restype = C.c_int64
-L.rd_wgrad_bf16_workspace_floats.restype = C.c_int64
 plans = [ts.mp.p1, ts.mp.p2] if getattr(ts, "mp", None) is not None else [ts.plan]
 seen, bad = set(), 0
 for pl in plans:

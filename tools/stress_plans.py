@@ -8,7 +8,6 @@ sys.path.insert(0, ".")
 from radar_depth_amd import convdesc as cd
 from radar_depth_amd._lib import check, current_stream, lib, ptr
 L = lib()
-L.rd_gconv_workspace_floats.restype = C.c_int64
 n, h, w, ci, co = (int(v) for v in sys.argv[1:6])
 reps = int(sys.argv[6]) if len(sys.argv) > 6 else 60
 mode = sys.argv[7] if len(sys.argv) > 7 else "1"

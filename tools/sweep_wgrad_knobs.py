@@ -16,7 +16,6 @@ def child():
     from radar_depth_amd.synthetic import procedural_fill_
     from tools.bench_ops import timeit
     L = lib()
-    L.rd_wgrad_workspace_floats.restype = C.c_int64
     args = types.SimpleNamespace(arch="resnet18_latefusion", decoder="upproj", modality="rgbd", pretrained=False)
     torch.manual_seed(0)
     m = create_model(args, [450, 800])

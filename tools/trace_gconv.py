@@ -39,7 +39,6 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record(); ops.gconv(d, x, wp, y); e1.record(); torch.cuda.synchronize()
 kernel_us = e0.elapsed_time(e1) * 1e3
 buf = np.zeros((nwg, 64), dtype=np.uint64)
-L.rd_gconv_trace_read.argtypes = [C.c_void_p, C.c_int]
 assert L.rd_gconv_trace_read(buf.ctypes.data, nwg) == 0
 n = int(buf[0, 0]); st = buf[:, 1:1 + n].astype(np.int64)
 print("kernel %.1f us by events (= %.0fk cycles at 2.4 GHz)" % (kernel_us, kernel_us * 2.4))
