@@ -498,6 +498,11 @@ int rd_bnact_maxpool_bwd_stats(const float* dy, int32_t lddy, const uint8_t* idx
 /* ---------------------------------------------------------------------------------------
  * Head: conv3 (3x3, C->1, models.py:587,661) and bilinear align_corners=True resize
  * (models.py:588,662).  d is NHWC-1 / NCHW-1 (same memory) [N,Hs,Ws]; out is [N,1,Ho,Wo].
+ * Arguments (these and the _t forms below; -1 and rd_last_error naming the entry point, before
+ * anything is launched): C == 16; N, H, W >= 1; x / dx are channel windows, ldx / lddx a
+ * multiple of 4 and >= C, the pointer aligned to four elements (16 B fp32, 8 B bf16); ws
+ * 16-byte aligned.  dw_oihw is overwritten, not accumulated into.  The bilinear weight is
+ * fl(scale * o - i0), fused (csrc/head.hip, src_index).
  * ------------------------------------------------------------------------------------- */
 int rd_head_conv_fwd(const float* x, int32_t ldx, const float* w_oihw, int32_t N, int32_t H, int32_t W,
                      int32_t C, float* d, void* stream);

@@ -267,7 +267,10 @@ __global__ __launch_bounds__(256) void head_conv_wgrad_kernel(const T* __restric
     }
 }
 
-// align_corners=True bilinear; scale and source index computed in fp32 exactly as ATen does for float tensors
+// align_corners=True bilinear, scale and source index in fp32 as ATen has them for float tensors -- except the weight: the compiler contracts
+// src - (float)i0 with the product into one fma, so l1 = fl(scale * o - i0) with a single rounding, not ATen's fl(fl(scale * o) - i0) (up to
+// u * src apart, 5e-5 at column 800, and the closer of the two to the exact coordinate); i0 is taken from the rounded product.  The clamp
+// keeps l1 in [0, 1] where the two disagree about the integer part (tests/head_ref.py bounds either form: 2u * src from the exact one).
 __device__ __forceinline__ void src_index(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
     const float src = scale * (float)o;
     i0 = (int)src;
@@ -378,12 +381,22 @@ static int head_wgrad_blocks(int64_t pixels) {
     return (int)(b > cap ? cap : (b < 1 ? 1 : b));
 }
 
+// argument checks shared by the head's launchers: C == 16 (four lanes per pixel), a non-empty map, and for a channel window (p, ld) of
+// element type T the 4-channel grid of ld4 / st4: ld a multiple of 4 and at least C, p aligned to four elements (16 B fp32, 8 B bf16)
+static bool head_geom_ok(int N, int H, int W, int C) { return C == 16 && N >= 1 && H >= 1 && W >= 1; }
+template <typename T>
+static bool head_window_ok(const T* p, int ld, int C) {
+    return p && ld % 4 == 0 && ld >= C && reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
+}
+static bool head_ws_ok(const float* ws) { return ws && reinterpret_cast<uintptr_t>(ws) % 16 == 0; }
+
 }  // namespace rd
 using namespace rd;
 
 template <typename T>
-static int head_conv_fwd_T(const T* x, int32_t ldx, const float* w_oihw, int32_t N, int32_t H, int32_t W, int32_t C, float* d, void* stream) {
-    RD_CHECK_ARG(x && w_oihw && d && C == 16 && ldx % 4 == 0, "head_conv_fwd: bad arguments (C must be 16)");
+static int head_conv_fwd_T(const char* who, const T* x, int32_t ldx, const float* w_oihw, int32_t N, int32_t H, int32_t W, int32_t C, float* d, void* stream) {
+    RD_CHECK_ARG(w_oihw && d && head_geom_ok(N, H, W, C), "%s: bad arguments (C must be 16; N, H, W >= 1)", who);
+    RD_CHECK_ARG(head_window_ok(x, ldx, C), "%s: x: ldx %d must be a multiple of 4 and >= C, the pointer aligned to four elements", who, ldx);
     static const bool tiled = !(getenv("RD_HEAD_FWD_TILED") && atoi(getenv("RD_HEAD_FWD_TILED")) == 0);
     const int tiles_h = cdiv(H, HT_H), tiles_w = cdiv(W, HT_W);
     if (tiled && (int64_t)N * tiles_h * tiles_w < (1ll << 31)) {
@@ -399,14 +412,14 @@ static int head_conv_fwd_T(const T* x, int32_t ldx, const float* w_oihw, int32_t
 }
 extern "C" int rd_head_conv_fwd(const float* x, int32_t ldx, const float* w_oihw, int32_t N, int32_t H, int32_t W, int32_t C,
                                 float* d, void* stream) {
-    return head_conv_fwd_T<float>(x, ldx, w_oihw, N, H, W, C, d, stream);
+    return head_conv_fwd_T<float>("rd_head_conv_fwd", x, ldx, w_oihw, N, H, W, C, d, stream);
 }
 // storage-typed form: x is an fp32 (RD_DTYPE_F32) or bf16 (RD_DTYPE_BF16) NHWC tensor; the depth map d stays fp32
 extern "C" int rd_head_conv_fwd_t(int32_t dtype, const void* x, int32_t ldx, const float* w_oihw, int32_t N, int32_t H, int32_t W,
                                   int32_t C, float* d, void* stream) {
-    if (dtype == RD_DTYPE_F32) return head_conv_fwd_T<float>(static_cast<const float*>(x), ldx, w_oihw, N, H, W, C, d, stream);
-    if (dtype == RD_DTYPE_BF16) return head_conv_fwd_T<bf16s>(static_cast<const bf16s*>(x), ldx, w_oihw, N, H, W, C, d, stream);
-    rd::set_error("head_conv_fwd_t: bad dtype %d", dtype);
+    if (dtype == RD_DTYPE_F32) return head_conv_fwd_T<float>("rd_head_conv_fwd_t", static_cast<const float*>(x), ldx, w_oihw, N, H, W, C, d, stream);
+    if (dtype == RD_DTYPE_BF16) return head_conv_fwd_T<bf16s>("rd_head_conv_fwd_t", static_cast<const bf16s*>(x), ldx, w_oihw, N, H, W, C, d, stream);
+    rd::set_error("rd_head_conv_fwd_t: bad dtype %d", dtype);
     return RD_EINVAL;
 }
 
@@ -418,8 +431,9 @@ extern "C" int64_t rd_head_conv_bwd_workspace_floats(int32_t N, int32_t H, int32
 // the two halves of the backward: the input gradient is what the rest of the backward waits for, the weight gradient (+ its slab
 // reduction) gates nothing until the gradient bucket closes -- callers may put it on another stream (engine.py does)
 template <typename T>
-static int head_conv_dgrad_T(const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C, T* dx, int32_t lddx, void* stream) {
-    RD_CHECK_ARG(w_oihw && dd && dx && C == 16 && lddx % 4 == 0, "head_conv_dgrad: bad arguments (C must be 16)");
+static int head_conv_dgrad_T(const char* who, const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C, T* dx, int32_t lddx, void* stream) {
+    RD_CHECK_ARG(w_oihw && dd && head_geom_ok(N, H, W, C), "%s: bad arguments (C must be 16; N, H, W >= 1)", who);
+    RD_CHECK_ARG(head_window_ok(dx, lddx, C), "%s: dx: lddx %d must be a multiple of 4 and >= C, the pointer aligned to four elements", who, lddx);
     static const bool tiled = !(getenv("RD_HEAD_DGRAD_TILED") && atoi(getenv("RD_HEAD_DGRAD_TILED")) == 0);
     const int tiles_h = cdiv(H, HT_H), tiles_w = cdiv(W, HT_W);
     if (tiled && (int64_t)N * tiles_h * tiles_w < (1ll << 31)) {
@@ -434,9 +448,11 @@ static int head_conv_dgrad_T(const float* w_oihw, const float* dd, int32_t N, in
     return RD_OK;
 }
 template <typename T>
-static int head_conv_wgrad_T(const T* x, int32_t ldx, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C, float* dw_oihw, float* ws,
+static int head_conv_wgrad_T(const char* who, const T* x, int32_t ldx, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C, float* dw_oihw, float* ws,
                              void* stream) {
-    RD_CHECK_ARG(x && dd && dw_oihw && ws && C == 16 && ldx % 4 == 0, "head_conv_wgrad: bad arguments (C must be 16)");
+    RD_CHECK_ARG(dd && dw_oihw && head_geom_ok(N, H, W, C), "%s: bad arguments (C must be 16; N, H, W >= 1)", who);
+    RD_CHECK_ARG(head_window_ok(x, ldx, C), "%s: x: ldx %d must be a multiple of 4 and >= C, the pointer aligned to four elements", who, ldx);
+    RD_CHECK_ARG(head_ws_ok(ws), "%s: ws must be given and 16-byte aligned", who);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t pixels = (int64_t)N * H * W;
     const int blocks = head_wgrad_blocks(pixels);
@@ -446,41 +462,46 @@ static int head_conv_wgrad_T(const T* x, int32_t ldx, const float* dd, int32_t N
     return launch_slab_reduce(ws, blocks, E, ws + (int64_t)blocks * E, dw_oihw, 9, C, 1, 1, C, 0, 0, s);
 }
 template <typename T>
-static int head_conv_bwd_T(const T* x, int32_t ldx, const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C,
+static int head_conv_bwd_T(const char* who, const T* x, int32_t ldx, const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C,
                            T* dx, int32_t lddx, float* dw_oihw, float* ws, void* stream) {
-    const int rc = head_conv_dgrad_T<T>(w_oihw, dd, N, H, W, C, dx, lddx, stream);
-    return rc != RD_OK ? rc : head_conv_wgrad_T<T>(x, ldx, dd, N, H, W, C, dw_oihw, ws, stream);
+    // everything is checked before the first of the two halves launches: a refused call writes nothing
+    RD_CHECK_ARG(w_oihw && dd && dw_oihw && head_geom_ok(N, H, W, C), "%s: bad arguments (C must be 16; N, H, W >= 1)", who);
+    RD_CHECK_ARG(head_window_ok(x, ldx, C), "%s: x: ldx %d must be a multiple of 4 and >= C, the pointer aligned to four elements", who, ldx);
+    RD_CHECK_ARG(head_window_ok(dx, lddx, C), "%s: dx: lddx %d must be a multiple of 4 and >= C, the pointer aligned to four elements", who, lddx);
+    RD_CHECK_ARG(head_ws_ok(ws), "%s: ws must be given and 16-byte aligned", who);
+    const int rc = head_conv_dgrad_T<T>(who, w_oihw, dd, N, H, W, C, dx, lddx, stream);
+    return rc != RD_OK ? rc : head_conv_wgrad_T<T>(who, x, ldx, dd, N, H, W, C, dw_oihw, ws, stream);
 }
 extern "C" int rd_head_conv_dgrad_t(int32_t dtype, const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C, void* dx,
                                     int32_t lddx, void* stream) {
-    if (dtype == RD_DTYPE_F32) return head_conv_dgrad_T<float>(w_oihw, dd, N, H, W, C, static_cast<float*>(dx), lddx, stream);
-    if (dtype == RD_DTYPE_BF16) return head_conv_dgrad_T<bf16s>(w_oihw, dd, N, H, W, C, static_cast<bf16s*>(dx), lddx, stream);
-    rd::set_error("head_conv_dgrad_t: bad dtype %d", dtype);
+    if (dtype == RD_DTYPE_F32) return head_conv_dgrad_T<float>("rd_head_conv_dgrad_t", w_oihw, dd, N, H, W, C, static_cast<float*>(dx), lddx, stream);
+    if (dtype == RD_DTYPE_BF16) return head_conv_dgrad_T<bf16s>("rd_head_conv_dgrad_t", w_oihw, dd, N, H, W, C, static_cast<bf16s*>(dx), lddx, stream);
+    rd::set_error("rd_head_conv_dgrad_t: bad dtype %d", dtype);
     return RD_EINVAL;
 }
 extern "C" int rd_head_conv_wgrad_t(int32_t dtype, const void* x, int32_t ldx, const float* dd, int32_t N, int32_t H, int32_t W, int32_t C,
                                     float* dw_oihw, float* ws, void* stream) {
-    if (dtype == RD_DTYPE_F32) return head_conv_wgrad_T<float>(static_cast<const float*>(x), ldx, dd, N, H, W, C, dw_oihw, ws, stream);
-    if (dtype == RD_DTYPE_BF16) return head_conv_wgrad_T<bf16s>(static_cast<const bf16s*>(x), ldx, dd, N, H, W, C, dw_oihw, ws, stream);
-    rd::set_error("head_conv_wgrad_t: bad dtype %d", dtype);
+    if (dtype == RD_DTYPE_F32) return head_conv_wgrad_T<float>("rd_head_conv_wgrad_t", static_cast<const float*>(x), ldx, dd, N, H, W, C, dw_oihw, ws, stream);
+    if (dtype == RD_DTYPE_BF16) return head_conv_wgrad_T<bf16s>("rd_head_conv_wgrad_t", static_cast<const bf16s*>(x), ldx, dd, N, H, W, C, dw_oihw, ws, stream);
+    rd::set_error("rd_head_conv_wgrad_t: bad dtype %d", dtype);
     return RD_EINVAL;
 }
 extern "C" int rd_head_conv_bwd(const float* x, int32_t ldx, const float* w_oihw, const float* dd, int32_t N, int32_t H, int32_t W,
                                 int32_t C, float* dx, int32_t lddx, float* dw_oihw, float* ws, void* stream) {
-    return head_conv_bwd_T<float>(x, ldx, w_oihw, dd, N, H, W, C, dx, lddx, dw_oihw, ws, stream);
+    return head_conv_bwd_T<float>("rd_head_conv_bwd", x, ldx, w_oihw, dd, N, H, W, C, dx, lddx, dw_oihw, ws, stream);
 }
 extern "C" int rd_head_conv_bwd_t(int32_t dtype, const void* x, int32_t ldx, const float* w_oihw, const float* dd, int32_t N, int32_t H,
                                   int32_t W, int32_t C, void* dx, int32_t lddx, float* dw_oihw, float* ws, void* stream) {
     if (dtype == RD_DTYPE_F32)
-        return head_conv_bwd_T<float>(static_cast<const float*>(x), ldx, w_oihw, dd, N, H, W, C, static_cast<float*>(dx), lddx, dw_oihw, ws, stream);
+        return head_conv_bwd_T<float>("rd_head_conv_bwd_t", static_cast<const float*>(x), ldx, w_oihw, dd, N, H, W, C, static_cast<float*>(dx), lddx, dw_oihw, ws, stream);
     if (dtype == RD_DTYPE_BF16)
-        return head_conv_bwd_T<bf16s>(static_cast<const bf16s*>(x), ldx, w_oihw, dd, N, H, W, C, static_cast<bf16s*>(dx), lddx, dw_oihw, ws, stream);
-    rd::set_error("head_conv_bwd_t: bad dtype %d", dtype);
+        return head_conv_bwd_T<bf16s>("rd_head_conv_bwd_t", static_cast<const bf16s*>(x), ldx, w_oihw, dd, N, H, W, C, static_cast<bf16s*>(dx), lddx, dw_oihw, ws, stream);
+    rd::set_error("rd_head_conv_bwd_t: bad dtype %d", dtype);
     return RD_EINVAL;
 }
 
 extern "C" int rd_bilinear_fwd(const float* d, int32_t N, int32_t Hs, int32_t Ws, float* out, int32_t Ho, int32_t Wo, void* stream) {
-    RD_CHECK_ARG(d && out && N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "bilinear_fwd: bad arguments");
+    RD_CHECK_ARG(d && out && N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "rd_bilinear_fwd: bad arguments (pointers; N, Hs, Ws, Ho, Wo >= 1)");
     const float sh = Ho > 1 ? (float)(Hs - 1) / (float)(Ho - 1) : 0.f;
     const float sw = Wo > 1 ? (float)(Ws - 1) / (float)(Wo - 1) : 0.f;
     hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(ew_grid64((int64_t)N * Ho * Wo)), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -490,7 +511,7 @@ extern "C" int rd_bilinear_fwd(const float* d, int32_t N, int32_t Hs, int32_t Ws
 }
 
 extern "C" int rd_bilinear_bwd(const float* dout, int32_t N, int32_t Ho, int32_t Wo, float* dd, int32_t Hs, int32_t Ws, void* stream) {
-    RD_CHECK_ARG(dout && dd && N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "bilinear_bwd: bad arguments");
+    RD_CHECK_ARG(dout && dd && N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "rd_bilinear_bwd: bad arguments (pointers; N, Hs, Ws, Ho, Wo >= 1)");
     const float sh = Ho > 1 ? (float)(Hs - 1) / (float)(Ho - 1) : 0.f;
     const float sw = Wo > 1 ? (float)(Ws - 1) / (float)(Wo - 1) : 0.f;
     hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(ew_grid64((int64_t)N * Hs * Ws)), dim3(256), 0, static_cast<hipStream_t>(stream),
