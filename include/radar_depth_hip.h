@@ -860,7 +860,9 @@ int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t 
  *                       u_packed: rd_wino_packed_bytes(O, I, flip) bytes.
  *   rd_wino_conv3x3   : out[N,H,W,Cout (stride ldo)] = conv3x3(in[N,H,W,Cin (stride ldi)]) (+ addend); stat_partial (may be NULL):
  *                       [rd_wino_stat_tiles(N,H,W)][2][Cout] per-tile sum / sum of squares of the stored values, the BatchNorm
- *                       statistics contract of rd_gconv.  fp32 NHWC tensors; Cin % 16 == 0, Cout % 64 == 0, both >= 64. */
+ *                       statistics contract of rd_gconv.  fp32 NHWC tensors; Cin % 16 == 0, Cout % 64 == 0, both >= 64.
+ *                       Refused with RD_EINVAL before anything is launched: a channel stride off the 4-element grid, `in` off 8 bytes,
+ *                       u_packed, out, addend (and bn_x, mean, scale, shift of the _bnbwd form) off 16 bytes. */
 int64_t rd_wino_packed_bytes(int32_t O, int32_t I, int32_t flip);
 int rd_wino_pack(const float* w_oihw, int32_t O, int32_t I, int32_t flip, void* u_packed, void* stream);
 int rd_wino_supported(int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ldi, int32_t ldo);

@@ -518,6 +518,11 @@ static int wino_launch(const float* in, int32_t N, int32_t H, int32_t W, int32_t
     RD_CHECK_ARG(in && u_packed && out && N > 0, "rd_wino_conv3x3: bad arguments");
     RD_CHECK_ARG(wino_shape_ok(H, W, Cin, Cout, ldi, ldo), "rd_wino_conv3x3: unsupported shape %dx%d %d->%d (ld %d / %d)", H, W, Cin, Cout, ldi, ldo);
     RD_CHECK_ARG(!addend || ld_add % 4 == 0, "rd_wino_conv3x3: addend stride %d", ld_add);
+    // the staging waves issue 8-byte loads from `in`; the weight fragments, out, addend, bn_x and the coefficient arrays move as 16-byte words
+    RD_CHECK_ARG(reinterpret_cast<uintptr_t>(in) % 8 == 0, "rd_wino_conv3x3: in is not 8-byte aligned");
+    RD_CHECK_ARG(aligned16(u_packed) && aligned16(out) && aligned16(addend), "rd_wino_conv3x3: u_packed, out or addend is not 16-byte aligned");
+    RD_CHECK_ARG(!bn_x || (aligned16(bn_x) && aligned16(bn_mean) && aligned16(bn_scale) && aligned16(bn_shift)),
+                 "rd_wino_conv3x3_bnbwd: bn_x, mean, scale or shift is not 16-byte aligned");
     WinoArgs a;
     a.in = in;
     a.u = static_cast<const unsigned short*>(u_packed);

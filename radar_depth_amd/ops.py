@@ -348,5 +348,20 @@ def wino_conv3x3(x_nhwc, u_packed, out_nhwc, addend=None, stat=None):
     return out_nhwc
 
 
+def wino_conv3x3_bnbwd(dy_nhwc, u_packed_flip, dx_nhwc, bn_x, mean, scale, shift, act, red_partial):
+    """The input gradient of a Winograd layer (u_packed_flip = wino_pack(w, flip=True)) that also emits the backward sums of the BatchNorm
+    in front of the convolution: red_partial [wino_stat_tiles][3][C], slot 0 = sum g, slot 1 = sum g (bn_x - mean), g = dx * act'."""
+    n, h, w, cin = dy_nhwc.shape
+    cout = dx_nhwc.shape[3]
+    for t in (dy_nhwc, dx_nhwc, bn_x):
+        assert t.dtype == torch.float32 and t.is_cuda and t.stride(3) == 1 and t.stride(1) == t.shape[2] * t.stride(2) and t.stride(0) == t.shape[1] * t.stride(1), \
+            "expected an NHWC CUDA float32 tensor (a channel slice of a wider buffer is fine)"
+    assert bn_x.shape == dx_nhwc.shape and tuple(red_partial.shape) == (wino_stat_tiles(n, h, w), 3, cout) and red_partial.is_contiguous()
+    check(lib().rd_wino_conv3x3_bnbwd(ptr(dy_nhwc), n, h, w, cin, dy_nhwc.stride(2), ptr(u_packed_flip), ptr(dx_nhwc), cout, dx_nhwc.stride(2),
+                                      ptr(bn_x), bn_x.stride(2), ptr(_f32(mean)), ptr(_f32(scale)), ptr(_f32(shift)), int(act), ptr(red_partial),
+                                      current_stream()), "rd_wino_conv3x3_bnbwd")
+    return dx_nhwc
+
+
 def wino_stat_tiles(n, h, w):
     return int(lib().rd_wino_stat_tiles(n, h, w))
