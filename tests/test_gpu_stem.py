@@ -54,7 +54,7 @@ def test_stem_forward(cfg):
     (1, 3, 64, 15, 63),       # a single ragged tile row
 ])
 def test_stem_forward_split(cfg):
-    """rd_stem_fwd_split (csrc/stem_bf16.hip, NP = 3: input and weights split into three bf16 pieces while staged, six MFMAs per product,
+    """rd_stem_fwd_split (csrc/stem_split.hip: input and weights split into three bf16 pieces while staged, six MFMAs per product,
     fp32 accumulation) against an fp64 convolution: as close as the fp32-MFMA stem (2e-6 of the output's max magnitude here; the fp32
     kernel is held to 2e-5 against torch CPU fp32), same partial-sum layout, inputs spanning 2^-20 .. 2^20 in magnitude."""
     from radar_depth_amd._lib import check, current_stream, lib, ptr

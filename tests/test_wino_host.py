@@ -200,7 +200,7 @@ def test_refusals_before_anything_is_launched():
     assert refused == 44
 
 
-@pytest.mark.parametrize("kernel", WC.FLAT_KERNELS)
+@pytest.mark.parametrize("kernel", WC.FLAT_ALL)
 def test_flat_lattice_premise_and_kept_terms(kernel):
     """The classes without the transform (the other forward kernels of the split family): the premise is asserted with the data; all
     six terms give the float64 result exactly; a removed term changes exactly the classes that claim it."""
@@ -211,3 +211,27 @@ def test_flat_lattice_premise_and_kept_terms(kernel):
             got = WC.flat_emulate(d, x, w, drop=term)
             changed = int(((got != want) & ~np.isnan(want)).sum())
             assert (changed > 0) == (term in WC.LATTICE[cls]), (kernel, cls, term, changed)
+
+
+def test_flat_tile_kinds_are_what_the_forced_tile_file_needs():
+    """tests/test_gpu_split_lattice_tiles.py: the library's own plan runs every kind on the 1x1 tile (so only the forced configurations
+    reach the other forms), none of them is a one-tap descriptor on gemm1_split (plan marker 1000), and the phases have the tap counts
+    the kinds are named for."""
+    L = _L()
+    prev = L.rd_gconv_split_plan_all(1)
+    try:
+        taps = {}
+        for kernel in ("gconv_split_3x3", "gconv_split_pre_3x3") + WC.FLAT_TILE_KERNELS:
+            d, slabs = WC.flat_desc(kernel)
+            pre = "_pre_" in kernel
+            info = (C.c_int32 * 8)()
+            assert (L.rd_gconv_split_pre_supported if pre else L.rd_gconv_split_supported)(C.byref(d)) == 1, kernel
+            assert (L.rd_gconv_split_pre_plan_info if pre else L.rd_gconv_split_plan_info)(C.byref(d), info) == 0
+            assert list(info[:2]) == [1, 1] and info[7] != 1000, (kernel, list(info))
+            kind = kernel[len("gconv_split_pre_" if pre else "gconv_split_"):]
+            taps[kind] = [d.phase[i].n_taps for i in range(d.n_phases)]
+            assert 1 + max(d.phase[i].widx[t] for i in range(d.n_phases) for t in range(d.phase[i].n_taps)) == slabs == WC.FLAT_TILE_KINDS[kind]
+            assert (d.Cin, d.Cout) == ((96, 96) if kind == "3x3_partial" else (64, 64)) and d.N == 2
+        assert taps == {"3x3": [9], "upproj_fwd": [9, 6, 6, 4], "dgrad_s2": [1, 2, 2, 4], "upproj_dgrad": [25], "3x3_partial": [9]}
+    finally:
+        L.rd_gconv_split_plan_all(1 if prev == 1 else 0)

@@ -395,6 +395,15 @@ def run_lattice(c):
 #   `per` non-zero weights per output channel keep every partial sum below 2^24 quanta (asserted).
 FLAT_KERNELS = ("gconv_split_3x3", "gconv_split_1x1", "gconv_split_pre_3x3", "gconv_split_pre_1x1", "gemm_taps_split_deconv2", "conv16_split")
 FLAT_PER = {"A": 16, "B": 16, "C": 8}
+# The descriptor kinds tests/test_gpu_split_lattice_tiles.py runs under every forced tile, for rd_gconv_split and rd_gconv_split_pre:
+# kind -> weight slabs.  Multi-phase descriptors with short last tap groups, a 25-tap single phase and a 3x3 with partial channel blocks.
+FLAT_TILE_KINDS = {"3x3": 9,                # conv_fwd(2, 7, 10, 64, 64, 3, 1, 1): the descriptor of FLAT_KERNELS
+                   "upproj_fwd": 25,        # phases of 9 / 6 / 6 / 4 taps
+                   "dgrad_s2": 9,           # conv_dgrad(2, 7, 10, 64, 64, 3, 2, 1): phases of 1 / 2 / 2 / 4 taps
+                   "upproj_dgrad": 25,      # one phase of 25 taps
+                   "3x3_partial": 9}        # conv_fwd(2, 13, 35, 96, 96, 3, 1, 1): partial 64-channel blocks on both sides
+FLAT_TILE_KERNELS = tuple("%s_%s" % (e, k) for e in ("gconv_split", "gconv_split_pre") for k in FLAT_TILE_KINDS if k != "3x3")
+FLAT_ALL = FLAT_KERNELS + FLAT_TILE_KERNELS          # (a kernel's index here seeds its data)
 
 
 def flat_desc(kernel):
@@ -404,16 +413,22 @@ def flat_desc(kernel):
         return cd.conv_fwd(2, 7, 10, 16, 16, 3, 1, 1), 9
     if kernel == "gemm_taps_split_deconv2":
         return cd.deconv_fwd(2, 5, 4, 64, 64, 2), 4
+    if kernel in FLAT_TILE_KERNELS:
+        kind = kernel[len("gconv_split_pre_" if "_pre_" in kernel else "gconv_split_"):]
+        d = {"upproj_fwd": lambda: cd.upproj_fwd(2, 7, 10, 64, 64), "dgrad_s2": lambda: cd.conv_dgrad(2, 7, 10, 64, 64, 3, 2, 1)[0],
+             "upproj_dgrad": lambda: cd.upproj_dgrad(2, 7, 10, 64, 64), "3x3_partial": lambda: cd.conv_fwd(2, 13, 35, 96, 96, 3, 1, 1)}[kind]()
+        return d, FLAT_TILE_KINDS[kind]
     k = 3 if kernel.endswith("3x3") else 1
     return cd.conv_fwd(2, 7, 10, 64, 64, k, 1, k // 2), k * k
 
 
+@functools.lru_cache(maxsize=None)
 def flat_data(kernel, cls, e=0):
     """-> (descriptor, x [N,Hi,Wi,Cin] float32, w [slabs,Cin,Cout] float32, float64 result with NaN where no phase writes)."""
     import torch
     from desc_emulator import run_desc
     d, S = flat_desc(kernel)
-    rng = np.random.default_rng([33, FLAT_KERNELS.index(kernel), "ABC".index(cls)])
+    rng = np.random.default_rng([33, FLAT_ALL.index(kernel), "ABC".index(cls)])
     shape = (d.N, d.Hi, d.Wi, d.Cin)
     per = min(FLAT_PER[cls], S * d.Cin)
     if cls == "A":
@@ -451,6 +466,13 @@ def flat_emulate(d, x, w, drop=None):
 def run_flat(kernel, cls):
     """One launch of the kernel on the class under poisoned LDS into a NaN-filled output -> (descriptor's plan marker or None,
     elements that differ from the float64 result, the first few)."""
+    plan, n_bad, first = run_flat_plan(kernel, cls)
+    return (None if plan is None else plan[7]), n_bad, first
+
+
+def run_flat_plan(kernel, cls):
+    """run_flat with the whole plan: -> (rd_gconv_split[_pre]_plan_info's eight figures under the tile choice of THIS process or None,
+    differing elements, the first few)."""
     import torch
     from radar_depth_amd import ops
     from radar_depth_amd._lib import check, current_stream, lib
@@ -459,7 +481,7 @@ def run_flat(kernel, cls):
     xg = torch.from_numpy(x).cuda()
     w_oihw = torch.from_numpy(np.ascontiguousarray(w.transpose(2, 1, 0)[..., None])).cuda()          # [Cout][Cin][slabs][1]
     out = torch.full((d.N, d.Ho, d.Wo, d.Cout), float("nan"), device="cuda")
-    marker = None
+    plan = None
     prev = L.rd_gconv_split_plan_all(1)
     try:
         check(L.rd_debug_poison_lds(st), "rd_debug_poison_lds")
@@ -475,7 +497,7 @@ def run_flat(kernel, cls):
             info = (C.c_int32 * 8)()
             assert (L.rd_gconv_split_pre_supported if pre else L.rd_gconv_split_supported)(C.byref(d)) == 1, kernel
             assert (L.rd_gconv_split_pre_plan_info if pre else L.rd_gconv_split_plan_info)(C.byref(d), info) == 0
-            marker = int(info[7])
+            plan = [int(v) for v in info]
             if pre:
                 ops.gconv_split_pre(d, ops.split_pieces(xg), ops.pack_weights_split(w_oihw), out)
             else:
@@ -486,4 +508,4 @@ def run_flat(kernel, cls):
     got = out.cpu().numpy().astype(D)
     assert np.array_equal(np.isnan(got), np.isnan(want)), "exactly the phases' pixels are written"
     bad = np.argwhere((got != want) & ~np.isnan(want))
-    return marker, len(bad), [(tuple(int(v) for v in i), float(got[tuple(i)]), float(want[tuple(i)])) for i in bad[:8]]
+    return plan, len(bad), [(tuple(int(v) for v in i), float(got[tuple(i)]), float(want[tuple(i)])) for i in bad[:8]]
