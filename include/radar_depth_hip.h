@@ -654,6 +654,25 @@ int rd_masked_berhu_bwd(const float* pred, const float* target, int64_t n, const
  * over a flat arena.  grad_scale multiplies g first (1/world for data-parallel averaging). */
 int rd_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd,
                 float grad_scale, int32_t first_step, void* stream);
+/* The same step behind torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False), and / or
+ * behind a guard against a non-finite gradient, without the norm leaving the device.  Two launches:
+ * rd_grad_sumsq: partials[rd_grad_sumsq_partials(n)] = per-workgroup sums of g[i]^2 in float64.  The grid is a function of n
+ *   alone, every order of addition is fixed and no atomics are used: the partials are bit-reproducible from call to call and equal
+ *   on every device.  The square of a float is exact in float64 and n of them cannot overflow it, so the sum S is finite exactly
+ *   when every element of g is.
+ * rd_sgd_step_clip: every workgroup adds the partials in one fixed order and forms, in float64,
+ *     total_norm = grad_scale * sqrt(S);   coef = (float)min(1, max_norm / (total_norm + 1e-6))    (a NaN stays a NaN, as torch.clamp)
+ *   max_norm <= 0 (or NaN): no clip, coef = 1.  Then rd_sgd_step's update with first_step = 0 and the float product grad_scale * coef
+ *   in place of grad_scale: coef == 1 gives rd_sgd_step's bits.  g is not written (it keeps the unclipped gradients).
+ *   skip_nonfinite != 0 and S not finite: p and buf are not touched.  Otherwise a non-finite S is not special-cased.
+ *   stats[4] (float64) = total_norm, coef, number of skipped calls so far (incremented, never reset), 1.0 if this call skipped else 0.0.
+ * g, p, buf, partials and stats are 16-byte aligned and n_partials == rd_grad_sumsq_partials(n); anything else returns RD_EINVAL
+ * before a launch. */
+int rd_grad_sumsq_partials(int64_t n);
+int rd_grad_sumsq(const float* g, int64_t n, double* partials, void* stream);
+int rd_sgd_step_clip(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, float grad_scale,
+                     double max_norm, int32_t skip_nonfinite, const double* partials, int32_t n_partials, double* stats,
+                     void* stream);
 int rd_fill(float* p, int64_t n, float v, void* stream);
 /* Input staging from the exported .h5 frames.  Replaces the depth decompression of
  * nuscenes_dataset_torch.get_data (dataset/nuscenes_dataset_torch_new.py:191-195) and the CenterCrop -> /255 -> ToTensor ->

@@ -137,6 +137,8 @@ std::string signature(const char* name, R (*)(A...)) {
     X(rd_gemm_taps_split_preferred) \
     X(rd_gemm_taps_split_stat_tiles) \
     X(rd_gemm_taps_split_supported) \
+    X(rd_grad_sumsq) \
+    X(rd_grad_sumsq_partials) \
     X(rd_graph_begin) \
     X(rd_graph_destroy) \
     X(rd_graph_end) \
@@ -185,6 +187,7 @@ std::string signature(const char* name, R (*)(A...)) {
     X(rd_render_rows) \
     X(rd_render_workspace_bytes) \
     X(rd_sgd_step) \
+    X(rd_sgd_step_clip) \
     X(rd_smooth_bwd) \
     X(rd_smooth_fwd) \
     X(rd_smooth_workspace_floats) \

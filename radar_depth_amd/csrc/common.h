@@ -287,6 +287,26 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// Sum of a double over the wave's 64 lanes, valid in lane 63, on the vector ALU's DPP path: __shfl_xor compiles to ds_bpermute, and the
+// 120 permutes per interval of a butterfly over ten doubles made the LDS pipe, which a CU's four SIMDs share, the bottleneck of the
+// distance-interval metrics (measured: 462 us at b = 16, 450x800 with every interval in every wave).  Pairs, quads, half rows and rows
+// of 16 by quad_perm and the two row mirrors; rows 1 and 3 then take lane 15 / 47 of the row below, rows 2 and 3 lane 31.  Needs all
+// 64 lanes active; the order of the additions is fixed.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_add_d(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
+    return v + __hiloint2double(hi, lo);                    // (rows outside ROW_MASK add +0.0)
+}
+__device__ __forceinline__ double wave_total_lane63(double v) {
+    v = dpp_add_d<0xB1, 0xF>(v);        // quad_perm [1,0,3,2]
+    v = dpp_add_d<0x4E, 0xF>(v);        // quad_perm [2,3,0,1]
+    v = dpp_add_d<0x141, 0xF>(v);       // row_half_mirror
+    v = dpp_add_d<0x140, 0xF>(v);       // row_mirror
+    v = dpp_add_d<0x142, 0xA>(v);       // row_bcast:15 into rows 1 and 3
+    v = dpp_add_d<0x143, 0xC>(v);       // row_bcast:31 into rows 2 and 3
+    return v;
+}
 __device__ __forceinline__ float act_fwd(float z, int act) {
     if (act == RD_ACT_RELU) return z > 0.f ? z : 0.f;
     if (act == RD_ACT_LEAKY02) return z > 0.f ? z : 0.2f * z;

@@ -508,6 +508,88 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     }
 }
 
+// ---------------------------------------------------------------- global gradient-norm clip and non-finite guard
+// torch.nn.utils.clip_grad_norm_(parameters, c, 2.0) between backward and optimizer.step(), without the norm leaving the device: pass 1
+// leaves one float64 sum of squares per block, every block of the SGD launch adds those (<= RED_BLOCKS words, as the second BerHu pass
+// takes its maxima) and forms the coefficient itself.  No atomics; every order is fixed by n alone: a thread's elements in grid-stride
+// order, the lanes' tree (wave_total_lane63), the four waves in order, the partials in thread-stride order and the same tree again.  So
+// the partials, the norm and the coefficient are bit-reproducible from call to call and equal on every rank of a data-parallel step.
+// A sum valid in EVERY thread of a 256-thread block (all lanes active).
+__device__ __forceinline__ double block_total_d(double v, double* sh) {
+    v = wave_total_lane63(v);
+    rd_sync();
+    if ((threadIdx.x & 63) == 63) sh[threadIdx.x >> 6] = v;
+    rd_sync();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+__device__ __forceinline__ double sumsq4(double a, const float4 v) {
+    a = fma((double)v.x, (double)v.x, a);
+    a = fma((double)v.y, (double)v.y, a);
+    a = fma((double)v.z, (double)v.z, a);
+    return fma((double)v.w, (double)v.w, a);
+}
+// The square of an fp32 value is exact in float64 (48 significant bits, at most 2^256), and 1.5e7 of them -- 2^31 of them -- cannot
+// overflow it: the sum is finite exactly when every element is finite.  The skip decision of sgd_clip_kernel rests on that.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n4, int64_t n, double* __restrict__ part) {
+    __shared__ double sh[4];
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double a = 0.0;
+    for (; e + 3 * stride < n4; e += 4 * stride) {          // four 16-byte loads in flight per lane; added in the order of the plain loop
+        const float4 v0 = g4[e], v1 = g4[e + stride], v2 = g4[e + 2 * stride], v3 = g4[e + 3 * stride];
+        a = sumsq4(sumsq4(sumsq4(sumsq4(a, v0), v1), v2), v3);
+    }
+    for (; e < n4; e += stride) a = sumsq4(a, g4[e]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const float x = g[(n4 << 2) + threadIdx.x];
+        a = fma((double)x, (double)x, a);
+    }
+    a = block_total_d(a, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// sgd_kernel's update (a momentum buffer always exists: first = 0) with gscale * coef in place of gscale, in the same operation order
+// and with the same fmafs: coef == 1.0f gives sgd_kernel's bits.  Every block forms S, the norm and the coefficient from the partials.
+__global__ __launch_bounds__(256) void sgd_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                       int64_t n4, int64_t n, float lr, float momentum, float wd, float gscale,
+                                                       double max_norm, int skip_nonfinite, const double* __restrict__ part, int n_part,
+                                                       double* __restrict__ stats) {
+    __shared__ double sh[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_part; i += blockDim.x) a += part[i];
+    const double S = block_total_d(a, sh);
+    const double total_norm = (double)gscale * sqrt(S);
+    const double r = max_norm / (total_norm + 1e-6);
+    const float coef = max_norm > 0.0 ? (float)(r > 1.0 ? 1.0 : r) : 1.f;      // torch.clamp(max=1): a NaN stays a NaN
+    const bool skip = skip_nonfinite && !isfinite(S);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        stats[0] = total_norm;
+        stats[1] = (double)coef;
+        if (skip) stats[2] += 1.0;
+        stats[3] = skip ? 1.0 : 0.0;
+    }
+    if (skip) return;                                                          // (block-uniform) before anything of p or buf is touched
+    const float s = gscale * coef;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
+        float4 pv = reinterpret_cast<float4*>(p)[e];
+        const float4 gv = reinterpret_cast<const float4*>(g)[e];
+        const float4 d = make_float4(fmaf(wd, pv.x, s * gv.x), fmaf(wd, pv.y, s * gv.y), fmaf(wd, pv.z, s * gv.z), fmaf(wd, pv.w, s * gv.w));
+        float4 b = reinterpret_cast<float4*>(buf)[e];
+        b.x = fmaf(momentum, b.x, d.x); b.y = fmaf(momentum, b.y, d.y); b.z = fmaf(momentum, b.z, d.z); b.w = fmaf(momentum, b.w, d.w);
+        reinterpret_cast<float4*>(buf)[e] = b;
+        pv.x -= lr * b.x; pv.y -= lr * b.y; pv.z -= lr * b.z; pv.w -= lr * b.w;
+        reinterpret_cast<float4*>(p)[e] = pv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t e = (n4 << 2) + threadIdx.x;
+        const float d = fmaf(wd, p[e], s * g[e]);
+        const float b = fmaf(momentum, buf[e], d);
+        buf[e] = b;
+        p[e] -= lr * b;
+    }
+}
+
 static int red_grid(int64_t n) {
     int64_t g = cdiv64(n, 256 * 8);
     if (g > RED_BLOCKS) g = RED_BLOCKS;
@@ -763,5 +845,30 @@ extern "C" int rd_sgd_step(float* p, const float* g, float* buf, int64_t n, floa
     hipLaunchKernelGGL(sgd_kernel, dim3(ew_grid2(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, buf, n / 4, n, lr,
                        momentum, wd, grad_scale, first_step);
     RD_CHECK_LAUNCH("sgd_kernel");
+    return RD_OK;
+}
+
+// One double per block of grad_sumsq_kernel: a function of n alone (never of the CU count), so every device forms the same partials.
+extern "C" int rd_grad_sumsq_partials(int64_t n) { return n > 0 ? red_grid(n) : 0; }
+
+extern "C" int rd_grad_sumsq(const float* g, int64_t n, double* partials, void* stream) {
+    RD_CHECK_ARG(g && partials && n > 0 && aligned16(g) && aligned16(partials),
+                 "grad_sumsq: bad arguments (the arena and the partials must be 16-byte aligned)");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(red_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), g, n / 4, n, partials);
+    RD_CHECK_LAUNCH("grad_sumsq_kernel");
+    return RD_OK;
+}
+
+extern "C" int rd_sgd_step_clip(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, float grad_scale,
+                                double max_norm, int32_t skip_nonfinite, const double* partials, int32_t n_partials, double* stats,
+                                void* stream) {
+    RD_CHECK_ARG(p && g && buf && partials && stats && n > 0, "sgd_step_clip: null argument or n < 1");
+    RD_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(buf) && aligned16(partials) && aligned16(stats),
+                 "sgd_step_clip: the arenas, the partials and the stats must be 16-byte aligned");
+    RD_CHECK_ARG(n_partials == red_grid(n), "sgd_step_clip: n_partials = %d, rd_grad_sumsq_partials(%lld) = %d", n_partials, (long long)n,
+                 red_grid(n));
+    hipLaunchKernelGGL(sgd_clip_kernel, dim3(ew_grid2(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, buf, n / 4, n, lr,
+                       momentum, wd, grad_scale, max_norm, skip_nonfinite, partials, n_partials, stats);
+    RD_CHECK_LAUNCH("sgd_clip_kernel");
     return RD_OK;
 }

@@ -18,27 +18,7 @@ struct MdBounds {
     float lo[MD_MAX], hi[MD_MAX];               // interval k = [lo[k], hi[k]], both closed; hi[n-1] = +inf
 };
 
-// Sum of a double over the wave's 64 lanes, valid in lane 63, on the vector ALU's DPP path: __shfl_xor compiles to ds_bpermute, and the
-// 120 permutes per interval of a butterfly over ten doubles made the LDS pipe, which a CU's four SIMDs share, the kernel's bottleneck
-// (measured: 462 us at b = 16, 450x800 with every interval in every wave).  Pairs, quads, half rows and rows of 16 by quad_perm and
-// the two row mirrors; rows 1 and 3 then take lane 15 / 47 of the row below, rows 2 and 3 lane 31.  Needs all 64 lanes active; the
-// order of the additions is fixed.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add_d(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, false);
-    return v + __hiloint2double(hi, lo);                    // (rows outside ROW_MASK add +0.0)
-}
-__device__ __forceinline__ double wave_total_lane63(double v) {
-    v = dpp_add_d<0xB1, 0xF>(v);        // quad_perm [1,0,3,2]
-    v = dpp_add_d<0x4E, 0xF>(v);        // quad_perm [2,3,0,1]
-    v = dpp_add_d<0x141, 0xF>(v);       // row_half_mirror
-    v = dpp_add_d<0x140, 0xF>(v);       // row_mirror
-    v = dpp_add_d<0x142, 0xA>(v);       // row_bcast:15 into rows 1 and 3
-    v = dpp_add_d<0x143, 0xC>(v);       // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
+// (wave_total_lane63, the fixed-order sum of a double over a wave on the DPP path: common.h)
 // A hundred fp64 accumulators per thread (ten terms x ten intervals) would live in scratch.  Instead a thread keeps the ten fp32
 // terms of its MD_PIX pixels and a bitmask of the intervals each is in; the wave then visits the intervals any of its lanes holds
 // (a ballot: a depth map is smooth, most waves see one or two), adds each lane's terms of that interval in fp64, reduces the ten

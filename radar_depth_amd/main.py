@@ -156,7 +156,8 @@ class HipTrainStep:
     fp32 tolerances unchanged; everything else is the fp32 path."""
 
     def __init__(self, model, batch, height, width, lr=0.01, momentum=0.9, weight_decay=1e-4, loss_weights=None, use_graph=False,
-                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None, metrics=False, berhu_thresh=0.2):
+                 operands=None, criterion="l1", comm="auto", storage="fp32", autotune=None, metrics=False, berhu_thresh=0.2,
+                 max_grad_norm=None, skip_nonfinite=False):
         """criterion: "l1" (MaskedL1Loss, the default of utils.parse_command), "l2" (MaskedMSELoss, `-c l2`, main.py:294-305) or "berhu"
         (MaskedBerHuLoss(berhu_thresh), `-c berhu`; its threshold thresh * max|target - pred| is formed on the device, so the step stays
         free of host synchronisation and capturable); on the multistage archs both stage losses are of the chosen kind.  Anything else
@@ -170,10 +171,20 @@ class HipTrainStep:
         is read back until meter.average() / meter.last() is called.
         metrics="multidist": all of that, plus the same bookkeeping per distance interval (Result_multidist / AverageMeter_multidist,
         evaluation/metrics.py:61-176): one binning pass over the prediction and one update behind the loss pass, into
-        self.meter_multidist (DeviceAverageMeter_multidist; self.meter_multidist_stage1 for the multistage archs, per rank too)."""
+        self.meter_multidist (DeviceAverageMeter_multidist; self.meter_multidist_stage1 for the multistage archs, per rank too).
+        max_grad_norm: c > 0 (float("inf"): measure the norm, never clip) = torch.nn.utils.clip_grad_norm_(model.parameters(), c) between
+        backward and the SGD update: every gradient is multiplied by min(1, c / (total_norm + 1e-6)), total_norm the L2 norm over all
+        parameter gradients (of the averaged gradients when data-parallel), formed in float64 on the device.  The gradient arena keeps
+        the unclipped values: the coefficient is applied inside the SGD launch.
+        skip_nonfinite: a step whose total_norm is not finite leaves every parameter and momentum element as it was and is counted in
+        self.skipped (BatchNorm running statistics and the meters have been updated by the forward by then, as under GradScaler).
+        Either option replaces the one SGD launch by two and keeps self.grad_stats (see grad_norm / clip_coef / skipped)."""
         from .model.multistage_model import ResNet_multistage
         if criterion not in CRITERIA:
             raise ValueError("[Error] Unknown criterion...")
+        self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.grad_stats = None
         # storage="bf16": NHWC activations and their gradients live in HBM as bf16 (implies bf16 conv operands); BatchNorm
         # statistics, losses, parameters, their gradients and the optimizer stay fp32 -- BASELINE.json configs 3 / 5
         assert storage in ("fp32", "bf16"), storage
@@ -217,6 +228,10 @@ class HipTrainStep:
         dev = self.plan.dev
         self.batch, self.height, self.width = batch, height, width
         self.lr, self.momentum, self.wd = lr, momentum, weight_decay
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            # total_norm, clip_coef, skipped steps, last step skipped: written by the step, never read by it
+            self.grad_stats = torch.zeros(4, dtype=torch.float64, device=dev)
+            self._sumsq_partials = torch.zeros(self.L.rd_grad_sumsq_partials(self.st["total"]), dtype=torch.float64, device=dev)
         from . import comm as _comm
         tdist = torch.distributed.is_available() and torch.distributed.is_initialized()
         assert comm in ("auto", "rccl", "torch"), comm
@@ -365,6 +380,45 @@ class HipTrainStep:
             self.lr = lr
             self._drop_graphs()
 
+    @staticmethod
+    def _checked_max_grad_norm(c):
+        if c is None:
+            return None
+        c = float(c)
+        if not c > 0.0:                                     # zero, negative, NaN
+            raise ValueError("HipTrainStep: max_grad_norm is None or a number > 0 (float('inf'): never clip), got %r" % (c,))
+        return c
+
+    def set_max_grad_norm(self, c):
+        """Change the clip threshold of a step built with max_grad_norm or skip_nonfinite (the value is baked into the op, as lr is: the
+        marshalled table and the graphs are dropped).  None or float("inf"): stop clipping; the norm is still measured."""
+        c = self._checked_max_grad_norm(c)
+        if self.grad_stats is None:
+            if c is not None:
+                raise RuntimeError("this HipTrainStep was built without max_grad_norm / skip_nonfinite: it has no norm pass to clip by")
+            return
+        if c is None and not self.skip_nonfinite:
+            c = float("inf")                                # the two launches and grad_stats stay; the coefficient is 1
+        if c != self.max_grad_norm:
+            self.max_grad_norm = c
+            self._drop_graphs()
+
+    # one synchronising copy each; None when the step was built with neither option
+    @property
+    def grad_norm(self):
+        """total_norm of the last step: the L2 norm of all (averaged) gradients before the clip."""
+        return None if self.grad_stats is None else float(self.grad_stats[0].item())
+
+    @property
+    def clip_coef(self):
+        """The coefficient the last step multiplied its gradients by (1.0 when the norm was within max_grad_norm)."""
+        return None if self.grad_stats is None else float(self.grad_stats[1].item())
+
+    @property
+    def skipped(self):
+        """Steps skipped so far because their total_norm was not finite (not checkpointed)."""
+        return None if self.grad_stats is None else int(self.grad_stats[2].item())
+
     def _drop_graphs(self):
         """Hyper-parameters are baked into the marshalled step (and its graphs): drop both, the next step rebuilds them."""
         for g in (self.graphs or {}).values():
@@ -431,9 +485,18 @@ class HipTrainStep:
 
     def _sgd_ops(self):
         st = self.st
-        return [("sgd_step", self.L.rd_sgd_step, (ptr(st["arena"]), ptr(st["grads"]), ptr(st["mom"]), st["total"], C.c_float(self.lr),
-                                                   C.c_float(self.momentum), C.c_float(self.wd), C.c_float(1.0 / self.world), 0,
-                                                   self.plan.streams[0]))]
+        s = self.plan.streams[0]
+        if self.grad_stats is None:
+            return [("sgd_step", self.L.rd_sgd_step, (ptr(st["arena"]), ptr(st["grads"]), ptr(st["mom"]), st["total"], C.c_float(self.lr),
+                                                       C.c_float(self.momentum), C.c_float(self.wd), C.c_float(1.0 / self.world), 0, s))]
+        # The norm over the whole gradient arena (its padding words are zero: never written, summed with zeros by the exchange), taken
+        # behind the exchange when data-parallel: every rank runs the same kernels on the same bits and forms the same coefficient.
+        part = self._sumsq_partials
+        return [("grad_sumsq", self.L.rd_grad_sumsq, (ptr(st["grads"]), st["total"], ptr(part), s)),
+                ("sgd_step_clip", self.L.rd_sgd_step_clip,
+                 (ptr(st["arena"]), ptr(st["grads"]), ptr(st["mom"]), st["total"], C.c_float(self.lr), C.c_float(self.momentum),
+                  C.c_float(self.wd), C.c_float(1.0 / self.world), C.c_double(self.max_grad_norm or 0.0), int(self.skip_nonfinite),
+                  ptr(part), part.numel(), ptr(self.grad_stats), s))]
 
     def _comm_ops(self, i):
         """Native exchange behind piece i: an event behind the piece on the step's stream (plus the segment's tails on the depth /
