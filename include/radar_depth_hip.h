@@ -673,6 +673,35 @@ int rd_grad_sumsq(const float* g, int64_t n, double* partials, void* stream);
 int rd_sgd_step_clip(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float wd, float grad_scale,
                      double max_norm, int32_t skip_nonfinite, const double* partials, int32_t n_partials, double* stats,
                      void* stream);
+/* torch.optim.Adam / AdamW (single-tensor form; amsgrad, maximize off) over the flat arenas p, g, m (exp_avg), v (exp_avg_sq), with
+ * the optimizer state on the device: neither the step count nor a hyper-parameter is an argument, so a marshalled call -- and a
+ * captured graph of it -- serves every step of a schedule.  The state is a block of RD_ADAM_BLOCK_WORDS float64 words:
+ *    0 lr   1 beta1   2 beta2   3 eps   4 weight_decay      written by the host only
+ *    5 t (an integer)   6 beta1^t   7 beta2^t               advanced by rd_adam_prepare: t + 1 and ONE multiplication each per step
+ *                                                           (a fresh state is t = 0, products 1; a restored one t multiplications)
+ *    8 1.0 if the last rd_adam_prepare skipped, else 0.0
+ *    9 s = (float)grad_scale * (float)clip_coef  (one fp32 product)     10 (float)weight_decay     11 (float)(1 - lr * weight_decay)
+ *   12 (float)(1 - beta1)   13 (float)beta2   14 (float)(1 - beta2)   15 bc2s = (float)sqrt(1 - beta2^t)   16 (float)eps
+ *   17 step_size = (float)(lr / (1 - beta1^t))              words 9..17: formed in float64, rounded to fp32 once, held widened
+ *   18, 19 unused
+ * rd_adam_prepare (one workgroup): with n_partials > 0 it adds the partials of rd_grad_sumsq over the n gradients in rd_sgd_step_clip's
+ *   order, forms total_norm, the coefficient and the skip decision as rd_sgd_step_clip does and writes the same stats[4]; with
+ *   n_partials == 0 (partials and stats null) the coefficient is 1 and nothing is skipped.  Word 8 is written; unless the step is
+ *   skipped, words 5..7 are advanced and words 9..17 formed.  A skipped step changes no other word.
+ * rd_adam_step: returns at once when word 8 is set.  Otherwise per element, every line one or more fp32 operations in the order
+ *   written, none contracted, division and square root correctly rounded:
+ *       g = s * g[i]
+ *       mode RD_ADAM,  word 10 != 0:  g = g + wd * p          mode RD_ADAMW, word 10 != 0:  p = p * (word 11)
+ *       m = m + omb1 * (g - m);   v = beta2 * v + (omb2 * g) * g;   d = sqrt(v) / bc2s + eps;   p = p - step_size * (m / d)
+ *   g is not written.  It reads the block and writes none of it, so the two calls are two launches.
+ * p, g, m, v, block, partials and stats are 16-byte aligned, n >= 1, n_partials is 0 or rd_grad_sumsq_partials(n), mode is one of
+ * the two; anything else returns RD_EINVAL before a launch. */
+#define RD_ADAM_BLOCK_WORDS 20
+#define RD_ADAM 0
+#define RD_ADAMW 1
+int rd_adam_prepare(double* block, int64_t n, float grad_scale, double max_norm, int32_t skip_nonfinite,
+                    const double* partials, int32_t n_partials, double* stats, void* stream);
+int rd_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int32_t mode, const double* block, void* stream);
 int rd_fill(float* p, int64_t n, float v, void* stream);
 /* Input staging from the exported .h5 frames.  Replaces the depth decompression of
  * nuscenes_dataset_torch.get_data (dataset/nuscenes_dataset_torch_new.py:191-195) and the CenterCrop -> /255 -> ToTensor ->

@@ -36,6 +36,8 @@ std::string signature(const char* name, R (*)(A...)) {
     X(rd_abi_entry) \
     X(rd_abi_version) \
     X(rd_act_gate_t) \
+    X(rd_adam_prepare) \
+    X(rd_adam_step) \
     X(rd_allreduce_bucket) \
     X(rd_berhu_workspace_floats) \
     X(rd_bilinear_bwd) \

@@ -78,6 +78,7 @@ const std::unordered_map<std::string, Entry>& registry() {
         RD_ENTRY(rd_masked_berhu_sums), RD_ENTRY(rd_masked_berhu_sums_metrics), RD_ENTRY(rd_masked_berhu_bwd),
         RD_ENTRY(rd_l1_total), RD_ENTRY(rd_smooth_fwd), RD_ENTRY(rd_smooth_bwd), RD_ENTRY(rd_uncertainty_total),
         RD_ENTRY(rd_radar_filter), RD_ENTRY(rd_sgd_step), RD_ENTRY(rd_grad_sumsq), RD_ENTRY(rd_sgd_step_clip),
+        RD_ENTRY(rd_adam_prepare), RD_ENTRY(rd_adam_step),
         RD_ENTRY(rd_event_record), RD_ENTRY(rd_stream_wait_event), RD_ENTRY(rd_allreduce_bucket), RD_ENTRY(rd_broadcast),
         RD_ENTRY(rd_debug_poison_lds),
         RD_ENTRY(rd_gconv_split_pre), RD_ENTRY(rd_wgrad_split_pre), RD_ENTRY(rd_split_pieces),
