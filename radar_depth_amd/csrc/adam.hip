@@ -8,7 +8,7 @@
 //
 // Every fp32 operation of the update is an operation of its own (no contraction anywhere in this file, no fmaf), the division and the
 // square root are the correctly rounded ones: a numpy float32 restatement reproduces the launch bit for bit (tests/adam_ref.py).
-#include "common.h"
+#include "step_tail.h"
 
 #pragma clang fp contract(off)
 
@@ -19,45 +19,21 @@ enum : int { W_LR = 0, W_BETA1, W_BETA2, W_EPS, W_WD, W_T, W_B1T, W_B2T, W_SKIP,
              W_EPSF, W_STEP };
 static_assert(W_STEP < RD_ADAM_BLOCK_WORDS, "the state block holds every word");
 
-// loss_opt.hip's block_total_d: a sum valid in every thread of a 256-thread block (all lanes active), in the same fixed order
-__device__ __forceinline__ double block_total_d(double v, double* sh) {
-    v = wave_total_lane63(v);
-    rd_sync();
-    if ((threadIdx.x & 63) == 63) sh[threadIdx.x >> 6] = v;
-    rd_sync();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-// The norm, the coefficient and the skip decision exactly as sgd_clip_kernel forms them (n_part > 0), then the advance of the block.
-__global__ __launch_bounds__(256) void adam_prepare_kernel(double* __restrict__ blk, float gscale, double max_norm, int skip_nonfinite,
-                                                           const double* __restrict__ part, int n_part, double* __restrict__ stats) {
+// The norm, the coefficient and the skip decision as the clipped SGD kernel forms them (clip_prologue, n_part > 0), then the advance of
+// the block.
+__global__ __launch_bounds__(256) void adam_prepare_kernel(double* __restrict__ blk, float gscale, ClipArgs clip) {
     __shared__ double sh[4];
-    float coef = 1.f;
-    bool skip = false;
-    if (n_part > 0) {                                                          // (uniform: every lane takes part in the sum)
-        double a = 0.0;
-        for (int i = threadIdx.x; i < n_part; i += blockDim.x) a += part[i];
-        const double S = block_total_d(a, sh);
-        const double total_norm = (double)gscale * sqrt(S);
-        const double r = max_norm / (total_norm + 1e-6);
-        coef = max_norm > 0.0 ? (float)(r > 1.0 ? 1.0 : r) : 1.f;              // torch.clamp(max=1): a NaN stays a NaN
-        skip = skip_nonfinite && !isfinite(S);
-        if (threadIdx.x == 0) {
-            stats[0] = total_norm;
-            stats[1] = (double)coef;
-            if (skip) stats[2] += 1.0;
-            stats[3] = skip ? 1.0 : 0.0;
-        }
-    }
+    ClipDecision d = {1.f, false};
+    if (clip.n_part > 0) d = clip_prologue(gscale, clip, sh);                  // (uniform: every lane takes part in the sum)
     if (threadIdx.x != 0) return;
-    blk[W_SKIP] = skip ? 1.0 : 0.0;
-    if (skip) return;                                                          // t, the products and the step's scalars stay as they were
+    blk[W_SKIP] = d.skip ? 1.0 : 0.0;
+    if (d.skip) return;                                                         // t, the products and the step's scalars stay as they were
     const double lr = blk[W_LR], b1 = blk[W_BETA1], b2 = blk[W_BETA2], eps = blk[W_EPS], wd = blk[W_WD];
     const double t = blk[W_T] + 1.0, b1t = blk[W_B1T] * b1, b2t = blk[W_B2T] * b2;
     blk[W_T] = t;
     blk[W_B1T] = b1t;
     blk[W_B2T] = b2t;
-    blk[W_S] = (double)(gscale * coef);                                        // one fp32 product, as in sgd_clip_kernel
+    blk[W_S] = (double)(gscale * d.coef);                                      // one fp32 product, as in the clipped SGD kernel
     blk[W_WDF] = (double)(float)wd;
     blk[W_DECAY] = (double)(float)(1.0 - lr * wd);
     blk[W_OMB1] = (double)(float)(1.0 - b1);
@@ -140,8 +116,8 @@ extern "C" int rd_adam_prepare(double* block, int64_t n, float grad_scale, doubl
                  "rd_adam_prepare: partials and stats come together with n_partials > 0, or not at all with n_partials = 0");
     RD_CHECK_ARG(n_partials == 0 || n_partials == rd_grad_sumsq_partials(n), "rd_adam_prepare: n_partials = %d, rd_grad_sumsq_partials(%lld) = %d",
                  n_partials, (long long)n, rd_grad_sumsq_partials(n));
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), block, grad_scale, max_norm,
-                       skip_nonfinite, partials, n_partials, stats);
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), block, grad_scale,
+                       ClipArgs{max_norm, skip_nonfinite, partials, n_partials, stats});
     RD_CHECK_LAUNCH("adam_prepare_kernel");
     return RD_OK;
 }
@@ -151,10 +127,7 @@ extern "C" int rd_adam_step(float* p, const float* g, float* m, float* v, int64_
     RD_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(block),
                  "rd_adam_step: the arenas and the state block must be 16-byte aligned");
     RD_CHECK_ARG(mode == RD_ADAM || mode == RD_ADAMW, "rd_adam_step: mode %d is neither RD_ADAM (0) nor RD_ADAMW (1)", mode);
-    int64_t grid = cdiv64(n / 4 + 1, 256);
-    const int64_t cap = (int64_t)num_cus() * 16;
-    if (grid > cap) grid = cap;
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n / 4, n,
+    hipLaunchKernelGGL(adam_step_kernel, dim3(ew_grid2(n / 4 + 1)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, n / 4, n,
                        mode == RD_ADAMW ? 1 : 0, block);
     RD_CHECK_LAUNCH("adam_step_kernel");
     return RD_OK;

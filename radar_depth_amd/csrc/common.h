@@ -307,6 +307,14 @@ __device__ __forceinline__ double wave_total_lane63(double v) {
     v = dpp_add_d<0x143, 0xC>(v);       // row_bcast:31 into rows 2 and 3
     return v;
 }
+// A sum valid in EVERY thread of a 256-thread block (all lanes active): the lanes' tree, then the four waves in order.  sh: 4 doubles.
+__device__ __forceinline__ double block_total_d(double v, double* sh) {
+    v = wave_total_lane63(v);
+    rd_sync();
+    if ((threadIdx.x & 63) == 63) sh[threadIdx.x >> 6] = v;
+    rd_sync();
+    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
 __device__ __forceinline__ float act_fwd(float z, int act) {
     if (act == RD_ACT_RELU) return z > 0.f ? z : 0.f;
     if (act == RD_ACT_LEAKY02) return z > 0.f ? z : 0.2f * z;

@@ -2,12 +2,10 @@
 // (main.py:416-445): MaskedL1Loss (evaluation/criteria_new.py:44-54), MaskedBerHuLoss (:57-81), SmoothnessLoss (:8-28), the
 // uncertainty-weighted total (main.py:423-429), Filter_layer (model/multistage_model.py:87-119) and
 // torch.optim.SGD with momentum + weight decay (main.py:285-290,445).  All scalars stay on the device.
-#include "common.h"
 #include "metric_terms.h"
+#include "step_tail.h"
 
 namespace rd {
-
-constexpr int RED_BLOCKS = 1024;
 
 __device__ __forceinline__ double block_sum_d(double v, double* sh) {
     v = wave_sum_d(v);
@@ -20,40 +18,8 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {
     return s;
 }
 
-// ---------------------------------------------------------------- masked L1
+// ---------------------------------------------------------------- masked L1 / L2
 // SQ = false: MaskedL1Loss (sum |t-p|); SQ = true: MaskedMSELoss (criteria_new.py:31-41, sum (t-p)^2)
-template <bool SQ>
-__global__ __launch_bounds__(256) void l1_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                         int64_t n, double* __restrict__ part) {
-    __shared__ double sh[4];
-    double s = 0.0, c = 0.0;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const float t = target[e];
-        if (t > 0.f) {
-            const float diff = t - pred[e];
-            s += SQ ? (double)(diff * diff) : (double)fabsf(diff);
-            c += 1.0;
-        }
-    }
-    s = block_sum_d(s, sh);
-    c = block_sum_d(c, sh);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = s;
-        part[2 * blockIdx.x + 1] = c;
-    }
-}
-
-__global__ __launch_bounds__(256) void pair_final_kernel(const double* __restrict__ part, int nblocks, int npairs,
-                                                         double* __restrict__ out) {
-    __shared__ double sh[4];
-    for (int k = 0; k < npairs; ++k) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += part[(size_t)i * npairs + k];
-        s = block_sum_d(s, sh);
-        if (threadIdx.x == 0) out[k] = s;
-    }
-}
-
 template <bool SQ>
 __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
                                                      const double* __restrict__ sums, const float* __restrict__ coef,
@@ -67,70 +33,6 @@ __global__ __launch_bounds__(256) void l1_bwd_kernel(const float* __restrict__ p
             g = SQ ? -2.f * diff * k : (diff > 0.f ? -k : (diff < 0.f ? k : 0.f));
         }
         dpred[e] = accumulate ? dpred[e] + g : g;
-    }
-}
-
-// ---------------------------------------------------------------- evaluation metrics (evaluation/metrics.py:34-58)
-// part[block][10]: count, sum d^2, sum |d|, sum |log10 o - log10 t|, sum |d|/t, #(r<1.25), #(r<1.25^2), #(r<1.25^3),
-// sum (1/o-1/t)^2, sum |1/o-1/t|   over pixels with t > 0, d = o - t, r = max(o/t, t/o)
-// the ten fp32 terms of one valid pixel: metric_terms (metric_terms.h)
-__global__ __launch_bounds__(256) void metrics_partial_kernel(const float* __restrict__ out, const float* __restrict__ target,
-                                                              int64_t n, double* __restrict__ part) {
-    __shared__ double sh[4];
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const float t = target[e];
-        if (t > 0.f) metric_terms(out[e], t, acc);
-    }
-    for (int k = 0; k < 10; ++k) {
-        const double s = block_sum_d(acc[k], sh);
-        if (threadIdx.x == 0) part[(size_t)blockIdx.x * 10 + k] = s;
-    }
-}
-
-// The loss pass of the training step with the metric sums riding along: part[block][12] = the two loss sums of l1_partial_kernel<SQ>
-// (same grid, same per-thread element order, same block_sum_d: bit-identical), then the ten sums of metrics_partial_kernel.
-template <bool SQ>
-__global__ __launch_bounds__(256) void l1_metrics_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                                 int64_t n, double* __restrict__ part) {
-    __shared__ double sh[4];
-    double s = 0.0, c = 0.0;
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const float t = target[e];
-        if (t > 0.f) {
-            const float o = pred[e];
-            const float diff = t - o;
-            s += SQ ? (double)(diff * diff) : (double)fabsf(diff);
-            c += 1.0;
-            metric_terms(o, t, acc);
-        }
-    }
-    s = block_sum_d(s, sh);
-    c = block_sum_d(c, sh);
-    double* o = part + (size_t)blockIdx.x * 12;
-    if (threadIdx.x == 0) {
-        o[0] = s;
-        o[1] = c;
-    }
-    for (int k = 0; k < 10; ++k) {
-        const double v = block_sum_d(acc[k], sh);
-        if (threadIdx.x == 0) o[2 + k] = v;
-    }
-}
-// pair_final_kernel's sums (same thread stride, same block_sum_d) over part[block][na + nb], written to two places
-__global__ __launch_bounds__(256) void split_final_kernel(const double* __restrict__ part, int nblocks, int na, int nb,
-                                                          double* __restrict__ out_a, double* __restrict__ out_b) {
-    __shared__ double sh[4];
-    const int stride = na + nb;
-    for (int k = 0; k < stride; ++k) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += part[(size_t)i * stride + k];
-        s = block_sum_d(s, sh);
-        if (threadIdx.x == 0) {
-            if (k < na) out_a[k] = s;
-            else out_b[k - na] = s;
-        }
     }
 }
 
@@ -199,60 +101,112 @@ __global__ __launch_bounds__(256) void berhu_max_kernel(const float* __restrict_
     if (threadIdx.x == 0) pmax[blockIdx.x] = m;
 }
 
-// part[block][2 (+ 10)]: sum of terms, count (then the ten metric sums: the grid, the per-thread element order and the block sums of
-// metrics_partial_kernel, so they come out bit-identical); the loss sums do not depend on MET
-template <bool MET>
-__global__ __launch_bounds__(256) void berhu_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
-                                                            double thresh, const unsigned* __restrict__ pmax, int nblocks,
-                                                            double* __restrict__ part) {
-    __shared__ double sh[4];
-    __shared__ unsigned shu[4];
-    const BerhuConsts k = berhu_consts(thresh * (double)__uint_as_float(blocks_max_u(pmax, nblocks, shu)));
+// ---------------------------------------------------------------- the masked-sum pass and its final pass
+// Evaluation metrics (evaluation/metrics.py:34-58), ten sums: count, sum d^2, sum |d|, sum |log10 o - log10 t|, sum |d|/t, #(r<1.25),
+// #(r<1.25^2), #(r<1.25^3), sum (1/o-1/t)^2, sum |1/o-1/t|   over pixels with t > 0, d = o - t, r = max(o/t, t/o)
+// the ten fp32 terms of one valid pixel: metric_terms (metric_terms.h)
+enum : int { LOSS_NONE = 0, LOSS_L1, LOSS_L2, LOSS_BERHU };
+// MaskedL1Loss: |t-p|; MaskedMSELoss (criteria_new.py:31-41): (t-p)^2; MaskedBerHuLoss: berhu_term
+template <int LOSS>
+__device__ __forceinline__ float loss_term(float diff, const BerhuConsts& k) {
+    if constexpr (LOSS == LOSS_BERHU) return berhu_term(fabsf(diff), k);
+    else if constexpr (LOSS == LOSS_L2) return diff * diff;
+    else return fabsf(diff);
+}
+// ONE pass over the valid pixels (t > 0) of hw elements of (pred, target) for every loss and for the metrics that ride along with it,
+// called by every thread of a block; a thread takes the elements e0, e0 + stride, ... (the kernel's grid-stride walk).  dst[(LOSS ? 2 : 0) + (MET ? 10 : 0)], this block's
+// sums: the sum of the loss terms, the count, then the ten metric sums.  A column depends neither on LOSS nor on MET: the grid
+// (red_grid(hw)), the per-thread element order and block_sum_d are the same in every form, so metrics riding along cannot move a
+// bit of a loss, and a frame of hw elements is reduced exactly as a tensor of hw elements is.
+template <int LOSS, bool MET>
+__device__ __forceinline__ void masked_sums(const float* __restrict__ pred, const float* __restrict__ target, int64_t hw,
+                                            int64_t e0, int64_t stride, const BerhuConsts& k, double* __restrict__ dst, double* sh) {
+    constexpr int NL = LOSS != LOSS_NONE ? 2 : 0;
     double s = 0.0, c = 0.0;
     double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t e = e0; e < hw; e += stride) {
         const float t = target[e];
         if (t > 0.f) {
             const float o = pred[e];
-            s += (double)berhu_term(fabsf(t - o), k);
-            c += 1.0;
-            if (MET) metric_terms(o, t, acc);
+            if constexpr (LOSS != LOSS_NONE) {
+                s += (double)loss_term<LOSS>(t - o, k);
+                c += 1.0;
+            }
+            if constexpr (MET) metric_terms(o, t, acc);
         }
     }
-    s = block_sum_d(s, sh);
-    c = block_sum_d(c, sh);
-    double* o = part + (size_t)blockIdx.x * (MET ? 12 : 2);
-    if (threadIdx.x == 0) {
-        o[0] = s;
-        o[1] = c;
+    if constexpr (LOSS != LOSS_NONE) {
+        s = block_sum_d(s, sh);
+        c = block_sum_d(c, sh);
+        if (threadIdx.x == 0) {
+            dst[0] = s;
+            dst[1] = c;
+        }
     }
-    if (MET) {
+    if constexpr (MET) {
         for (int i = 0; i < 10; ++i) {
             const double v = block_sum_d(acc[i], sh);
-            if (threadIdx.x == 0) o[2 + i] = v;
+            if (threadIdx.x == 0) dst[NL + i] = v;
         }
     }
 }
-// split_final_kernel's sums over part[block][2 + nb] (nb = 0: no metric sums), then out_a[2] = delta, out_a[3] = the maximum
-__global__ __launch_bounds__(256) void berhu_final_kernel(const double* __restrict__ part, const unsigned* __restrict__ pmax, int nblocks,
-                                                          int nb, double thresh, double* __restrict__ out_a, double* __restrict__ out_b) {
+// The pass of every whole-tensor sums entry point: part[block][(LOSS ? 2 : 0) + (MET ? 10 : 0)].
+// LOSS_BERHU: every block first reduces the maxima of berhu_max_kernel (one per block of this grid) and forms the three constants itself.
+template <int LOSS, bool MET>
+__global__ __launch_bounds__(256) void masked_pass_kernel(const float* __restrict__ pred, const float* __restrict__ target, int64_t n,
+                                                          double thresh, const unsigned* __restrict__ pmax, double* __restrict__ part) {
     __shared__ double sh[4];
-    __shared__ unsigned shu[4];
-    const int stride = 2 + nb;
+    BerhuConsts k = {};
+    if constexpr (LOSS == LOSS_BERHU) {
+        __shared__ unsigned shu[4];
+        k = berhu_consts(thresh * (double)__uint_as_float(blocks_max_u(pmax, gridDim.x, shu)));
+    }
+    masked_sums<LOSS, MET>(pred, target, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, k, part + (size_t)blockIdx.x * ((LOSS != LOSS_NONE ? 2 : 0) + (MET ? 10 : 0)), sh);
+}
+// The blocks' partials added column by column, by every thread of one block of `threads` threads: part[nblocks][NA + NB], the first NA
+// columns to out_a[NA], the others to out_b[NB]
+template <int NA, int NB>
+__device__ __forceinline__ void column_sums(const double* __restrict__ part, int nblocks, int threads, double* __restrict__ out_a,
+                                            double* __restrict__ out_b, double* sh) {
+    constexpr int stride = NA + NB;
     for (int k = 0; k < stride; ++k) {
         double s = 0.0;
-        for (int i = threadIdx.x; i < nblocks; i += blockDim.x) s += part[(size_t)i * stride + k];
+        for (int i = threadIdx.x; i < nblocks; i += threads) s += part[(size_t)i * stride + k];
         s = block_sum_d(s, sh);
         if (threadIdx.x == 0) {
-            if (k < 2) out_a[k] = s;
-            else out_b[k - 2] = s;
+            if (k < NA) out_a[k] = s;
+            else out_b[k - NA] = s;
         }
     }
-    const double m = (double)__uint_as_float(blocks_max_u(pmax, nblocks, shu));
-    if (threadIdx.x == 0) {
-        out_a[2] = thresh * m;
-        out_a[3] = m;
+}
+// The final pass of every whole-tensor sums entry point (one workgroup).  pmax (BerHu): then out_a[NA] = delta, out_a[NA + 1] = the maximum.
+template <int NA, int NB>
+__global__ __launch_bounds__(256) void final_sums_kernel(const double* __restrict__ part, const unsigned* __restrict__ pmax, int nblocks,
+                                                         double thresh, double* __restrict__ out_a, double* __restrict__ out_b) {
+    __shared__ double sh[4];
+    column_sums<NA, NB>(part, nblocks, blockDim.x, out_a, out_b, sh);
+    if (pmax) {                                                                // (grid-uniform)
+        __shared__ unsigned shu[4];
+        const double m = (double)__uint_as_float(blocks_max_u(pmax, nblocks, shu));
+        if (threadIdx.x == 0) {
+            out_a[NA] = thresh * m;
+            out_a[NA + 1] = m;
+        }
     }
+}
+// per-frame metric sums: grid (blocks per frame, frames), part[frame][block][10], then one workgroup per frame.  Kernels of their own
+// over masked_sums and column_sums: launched through the whole-tensor kernels' wider argument lists, rd_depth_metrics_frames measured
+// 0.4 us slower than with these.
+__global__ __launch_bounds__(256) void metrics_frames_partial_kernel(const float* __restrict__ out, const float* __restrict__ target,
+                                                                     int64_t hw, double* __restrict__ part) {
+    __shared__ double sh[4];
+    masked_sums<LOSS_NONE, true>(out + (size_t)blockIdx.y * hw, target + (size_t)blockIdx.y * hw, hw,
+                                 (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, BerhuConsts{},
+                                 part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 10, sh);
+}
+__global__ __launch_bounds__(256) void metrics_frames_final_kernel(const double* __restrict__ part, int nb, double* __restrict__ sums) {
+    __shared__ double sh[4];
+    column_sums<0, 10>(part + (size_t)blockIdx.x * nb * 10, nb, blockDim.x, nullptr, sums + (size_t)blockIdx.x * 10, sh);
 }
 
 // autograd of the reference's expression in its own fp32 steps: g = coef / count reaches diff through part1 (where in1) and through
@@ -277,35 +231,6 @@ __global__ __launch_bounds__(256) void berhu_bwd_kernel(const float* __restrict_
             g = d > 0.f ? -a : (d < 0.f ? a : 0.f);
         }
         dpred[e] = accumulate ? dpred[e] + g : g;
-    }
-}
-
-// per-frame metric sums: grid (blocks per frame, frames), part[frame][block][10]; each frame is reduced exactly as
-// metrics_partial_kernel reduces a tensor of hw elements (same blocks per frame, same element order)
-__global__ __launch_bounds__(256) void metrics_frames_partial_kernel(const float* __restrict__ out, const float* __restrict__ target,
-                                                                     int64_t hw, double* __restrict__ part) {
-    __shared__ double sh[4];
-    const float* o = out + (size_t)blockIdx.y * hw;
-    const float* tg = target + (size_t)blockIdx.y * hw;
-    double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < hw; e += (int64_t)gridDim.x * blockDim.x) {
-        const float t = tg[e];
-        if (t > 0.f) metric_terms(o[e], t, acc);
-    }
-    double* dst = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 10;
-    for (int k = 0; k < 10; ++k) {
-        const double s = block_sum_d(acc[k], sh);
-        if (threadIdx.x == 0) dst[k] = s;
-    }
-}
-__global__ __launch_bounds__(256) void metrics_frames_final_kernel(const double* __restrict__ part, int nb, double* __restrict__ sums) {
-    __shared__ double sh[4];
-    const double* p = part + (size_t)blockIdx.x * nb * 10;
-    for (int k = 0; k < 10; ++k) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < nb; i += blockDim.x) s += p[(size_t)i * 10 + k];
-        s = block_sum_d(s, sh);
-        if (threadIdx.x == 0) sums[(size_t)blockIdx.x * 10 + k] = s;
     }
 }
 
@@ -482,46 +407,8 @@ __global__ void l1_total_kernel(const double* sums, float* loss, float* coef) {
     coef[0] = 1.f;
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                  int64_t n4, int64_t n, float lr, float momentum, float wd, float gscale, int first) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
-        float4 pv = reinterpret_cast<float4*>(p)[e];
-        const float4 gv = reinterpret_cast<const float4*>(g)[e];
-        float4 b;
-        float4 d = make_float4(fmaf(wd, pv.x, gscale * gv.x), fmaf(wd, pv.y, gscale * gv.y), fmaf(wd, pv.z, gscale * gv.z),
-                               fmaf(wd, pv.w, gscale * gv.w));
-        if (first) b = d;
-        else {
-            b = reinterpret_cast<float4*>(buf)[e];
-            b.x = fmaf(momentum, b.x, d.x); b.y = fmaf(momentum, b.y, d.y); b.z = fmaf(momentum, b.z, d.z); b.w = fmaf(momentum, b.w, d.w);
-        }
-        reinterpret_cast<float4*>(buf)[e] = b;
-        pv.x -= lr * b.x; pv.y -= lr * b.y; pv.z -= lr * b.z; pv.w -= lr * b.w;
-        reinterpret_cast<float4*>(p)[e] = pv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t e = (n4 << 2) + threadIdx.x;
-        const float d = fmaf(wd, p[e], gscale * g[e]);
-        const float b = first ? d : fmaf(momentum, buf[e], d);
-        buf[e] = b;
-        p[e] -= lr * b;
-    }
-}
-
-// ---------------------------------------------------------------- global gradient-norm clip and non-finite guard
-// torch.nn.utils.clip_grad_norm_(parameters, c, 2.0) between backward and optimizer.step(), without the norm leaving the device: pass 1
-// leaves one float64 sum of squares per block, every block of the SGD launch adds those (<= RED_BLOCKS words, as the second BerHu pass
-// takes its maxima) and forms the coefficient itself.  No atomics; every order is fixed by n alone: a thread's elements in grid-stride
-// order, the lanes' tree (wave_total_lane63), the four waves in order, the partials in thread-stride order and the same tree again.  So
-// the partials, the norm and the coefficient are bit-reproducible from call to call and equal on every rank of a data-parallel step.
-// A sum valid in EVERY thread of a 256-thread block (all lanes active).
-__device__ __forceinline__ double block_total_d(double v, double* sh) {
-    v = wave_total_lane63(v);
-    rd_sync();
-    if ((threadIdx.x & 63) == 63) sh[threadIdx.x >> 6] = v;
-    rd_sync();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
+// ---------------------------------------------------------------- optimizer: sum of squares of the gradient, SGD
+// (the clip that joins the two: clip_prologue, step_tail.h)
 __device__ __forceinline__ double sumsq4(double a, const float4 v) {
     a = fma((double)v.x, (double)v.x, a);
     a = fma((double)v.y, (double)v.y, a);
@@ -529,7 +416,7 @@ __device__ __forceinline__ double sumsq4(double a, const float4 v) {
     return fma((double)v.w, (double)v.w, a);
 }
 // The square of an fp32 value is exact in float64 (48 significant bits, at most 2^256), and 1.5e7 of them -- 2^31 of them -- cannot
-// overflow it: the sum is finite exactly when every element is finite.  The skip decision of sgd_clip_kernel rests on that.
+// overflow it: the sum is finite exactly when every element is finite.  The skip decision of clip_prologue rests on that.
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n4, int64_t n, double* __restrict__ part) {
     __shared__ double sh[4];
     const float4* g4 = reinterpret_cast<const float4*>(g);
@@ -549,57 +436,55 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
     if (threadIdx.x == 0) part[blockIdx.x] = a;
 }
 
-// sgd_kernel's update (a momentum buffer always exists: first = 0) with gscale * coef in place of gscale, in the same operation order
-// and with the same fmafs: coef == 1.0f gives sgd_kernel's bits.  Every block forms S, the norm and the coefficient from the partials.
+__device__ __forceinline__ float fma_s(float a, float x, float y) { return fmaf(a, x, y); }
+__device__ __forceinline__ float4 fma_s(float a, const float4 x, const float4 y) {
+    return make_float4(fmaf(a, x.x, y.x), fmaf(a, x.y, y.y), fmaf(a, x.z, y.z), fmaf(a, x.w, y.w));
+}
+// torch.optim.SGD with momentum and weight decay (main.py:285-290,445) on one 16-byte word (V = float4) or one tail element (V = float):
+// d = wd p + s g; b = d on the first step (no momentum buffer yet: buf is not read), momentum b + d after it; p -= lr b.  ONE
+// definition for the loop and the tail of both SGD kernels, so that a coefficient of 1.0f (s = gscale) gives the unclipped
+// step's bits.
+template <class V>
+__device__ __forceinline__ void sgd_update(V* __restrict__ p, const V* __restrict__ g, V* __restrict__ buf, float lr, float momentum,
+                                           float wd, float s, bool first) {
+    V pv = *p;
+    V b = fma_s(wd, pv, s * *g);
+    if (!first) b = fma_s(momentum, *buf, b);
+    *buf = b;
+    pv -= lr * b;
+    *p = pv;
+}
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                  int64_t n4, int64_t n, float lr, float momentum, float wd, float gscale, int first) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x)
+        sgd_update(reinterpret_cast<float4*>(p) + e, reinterpret_cast<const float4*>(g) + e, reinterpret_cast<float4*>(buf) + e, lr, momentum,
+                   wd, gscale, first);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t e = (n4 << 2) + threadIdx.x;
+        sgd_update(p + e, g + e, buf + e, lr, momentum, wd, gscale, first);
+    }
+}
+// sgd_kernel's walk over sgd_update (a momentum buffer always exists: first = 0) with gscale * coef in place of gscale.  Every block
+// forms S, the norm and the coefficient from the partials (clip_prologue).  A kernel of its own: as one template with sgd_kernel both
+// entry points measured 0.2 us slower than the parent's kernels.  Each kernel reads blockDim.x / gridDim.x itself (read in an inlined
+// device function they compile through the non-uniform-workgroup path), so the walk is written in both.
 __global__ __launch_bounds__(256) void sgd_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                        int64_t n4, int64_t n, float lr, float momentum, float wd, float gscale,
                                                        double max_norm, int skip_nonfinite, const double* __restrict__ part, int n_part,
                                                        double* __restrict__ stats) {
     __shared__ double sh[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n_part; i += blockDim.x) a += part[i];
-    const double S = block_total_d(a, sh);
-    const double total_norm = (double)gscale * sqrt(S);
-    const double r = max_norm / (total_norm + 1e-6);
-    const float coef = max_norm > 0.0 ? (float)(r > 1.0 ? 1.0 : r) : 1.f;      // torch.clamp(max=1): a NaN stays a NaN
-    const bool skip = skip_nonfinite && !isfinite(S);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        stats[0] = total_norm;
-        stats[1] = (double)coef;
-        if (skip) stats[2] += 1.0;
-        stats[3] = skip ? 1.0 : 0.0;
-    }
-    if (skip) return;                                                          // (block-uniform) before anything of p or buf is touched
-    const float s = gscale * coef;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
-        float4 pv = reinterpret_cast<float4*>(p)[e];
-        const float4 gv = reinterpret_cast<const float4*>(g)[e];
-        const float4 d = make_float4(fmaf(wd, pv.x, s * gv.x), fmaf(wd, pv.y, s * gv.y), fmaf(wd, pv.z, s * gv.z), fmaf(wd, pv.w, s * gv.w));
-        float4 b = reinterpret_cast<float4*>(buf)[e];
-        b.x = fmaf(momentum, b.x, d.x); b.y = fmaf(momentum, b.y, d.y); b.z = fmaf(momentum, b.z, d.z); b.w = fmaf(momentum, b.w, d.w);
-        reinterpret_cast<float4*>(buf)[e] = b;
-        pv.x -= lr * b.x; pv.y -= lr * b.y; pv.z -= lr * b.z; pv.w -= lr * b.w;
-        reinterpret_cast<float4*>(p)[e] = pv;
-    }
+    const ClipDecision c = clip_prologue(gscale, ClipArgs{max_norm, skip_nonfinite, part, n_part, stats}, sh);
+    if (c.skip) return;                                                        // (block-uniform) before anything of p or buf is touched
+    const float s = gscale * c.coef;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x)
+        sgd_update(reinterpret_cast<float4*>(p) + e, reinterpret_cast<const float4*>(g) + e, reinterpret_cast<float4*>(buf) + e, lr, momentum,
+                   wd, s, false);
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t e = (n4 << 2) + threadIdx.x;
-        const float d = fmaf(wd, p[e], s * g[e]);
-        const float b = fmaf(momentum, buf[e], d);
-        buf[e] = b;
-        p[e] -= lr * b;
+        sgd_update(p + e, g + e, buf + e, lr, momentum, wd, s, false);
     }
 }
 
-static int red_grid(int64_t n) {
-    int64_t g = cdiv64(n, 256 * 8);
-    if (g > RED_BLOCKS) g = RED_BLOCKS;
-    return (int)(g < 1 ? 1 : g);
-}
-static int ew_grid2(int64_t n) {
-    int64_t g = cdiv64(n, 256);
-    const int64_t cap = (int64_t)num_cus() * 16;
-    return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
 constexpr int SM_BLOCKS = 256;  // blocks per sample in the smoothness passes (64 left the b = 8 passes of config 4 at two blocks per CU: smooth_main 157 us)
 
 }  // namespace rd
@@ -607,66 +492,65 @@ using namespace rd;
 
 extern "C" int rd_loss_tiles(int64_t n) { return red_grid(n); }
 
-// ws: 2*rd_loss_tiles(n) doubles (pass as float* with 4*tiles floats, 8-byte aligned)
-extern "C" int rd_masked_l1_sums(const float* pred, const float* target, int64_t n, float* ws, double* sums, void* stream) {
-    RD_CHECK_ARG(pred && target && ws && sums && n > 0 && ((uintptr_t)ws & 7) == 0, "masked_l1_sums: bad arguments");
+// The launches of every whole-tensor sums entry point (the argument checks are the entry point's own): berhu_max_kernel for LOSS_BERHU,
+// the masked pass, the final pass.  ws: doubles part[tiles][2 (a loss) + 10 (MET)], tiles = rd_loss_tiles(n); LOSS_BERHU: unsigned
+// pmax[tiles] at part + 12 * tiles, with and without metrics.  sums[2] (BerHu: [4]) and msums[10]; a form without a loss or without
+// metrics does not touch its pointer.
+template <int LOSS, bool MET>
+static int launch_sums(const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums, double* msums,
+                       void* stream) {
+    const auto launched = [](const char* kernel) {                             // a launch failure names the instantiation
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            set_error("%s<%s, %s>: %s", kernel, LOSS == LOSS_NONE ? "none" : LOSS == LOSS_L1 ? "L1" : LOSS == LOSS_L2 ? "L2" : "BerHu",
+                      MET ? "metrics" : "no metrics", hipGetErrorString(e));
+        return e == hipSuccess;
+    };
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int g = red_grid(n);
+    constexpr int NL = LOSS != LOSS_NONE ? 2 : 0;
     double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(l1_partial_kernel<false>, dim3(g), dim3(256), 0, s, pred, target, n, part);
-    RD_CHECK_LAUNCH("l1_partial_kernel");
-    hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, s, part, g, 2, sums);
-    RD_CHECK_LAUNCH("pair_final_kernel");
+    unsigned* pmax = nullptr;
+    if constexpr (LOSS == LOSS_BERHU) {
+        pmax = reinterpret_cast<unsigned*>(part + (size_t)12 * g);
+        hipLaunchKernelGGL(berhu_max_kernel, dim3(g), dim3(256), 0, s, pred, target, n, pmax);
+        RD_CHECK_LAUNCH("berhu_max_kernel");
+    }
+    hipLaunchKernelGGL((masked_pass_kernel<LOSS, MET>), dim3(g), dim3(256), 0, s, pred, target, n, thresh, pmax, part);
+    if (!launched("masked_pass_kernel")) return RD_ELAUNCH;
+    hipLaunchKernelGGL((final_sums_kernel<NL, MET ? 10 : 0>), dim3(1), dim3(256), 0, s, part, pmax, g, thresh, sums, msums);
+    if (!launched("final_sums_kernel")) return RD_ELAUNCH;
     return RD_OK;
+}
+
+// sums[0] = sum |t-p| over t>0, sums[1] = count.  ws: 2*rd_loss_tiles(n) doubles (pass as float* with 4*tiles floats, 8-byte aligned)
+extern "C" int rd_masked_l1_sums(const float* pred, const float* target, int64_t n, float* ws, double* sums, void* stream) {
+    RD_CHECK_ARG(pred && target && ws && sums && n > 0 && ((uintptr_t)ws & 7) == 0, "masked_l1_sums: bad arguments");
+    return launch_sums<LOSS_L1, false>(pred, target, n, 0.0, ws, sums, nullptr, stream);
 }
 // MaskedMSELoss (criteria_new.py:31-41): sums[0] = sum (t-p)^2 over t>0, sums[1] = count
 extern "C" int rd_masked_l2_sums(const float* pred, const float* target, int64_t n, float* ws, double* sums, void* stream) {
     RD_CHECK_ARG(pred && target && ws && sums && n > 0 && ((uintptr_t)ws & 7) == 0, "masked_l2_sums: bad arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int g = red_grid(n);
-    double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(l1_partial_kernel<true>, dim3(g), dim3(256), 0, s, pred, target, n, part);
-    RD_CHECK_LAUNCH("l2_partial_kernel");
-    hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, s, part, g, 2, sums);
-    RD_CHECK_LAUNCH("pair_final_kernel");
-    return RD_OK;
+    return launch_sums<LOSS_L2, false>(pred, target, n, 0.0, ws, sums, nullptr, stream);
 }
 
 // sums[10] as listed above; ws: 10*rd_loss_tiles(n) doubles
 extern "C" int rd_depth_metrics(const float* output, const float* target, int64_t n, float* ws, double* sums, void* stream) {
     RD_CHECK_ARG(output && target && ws && sums && n > 0 && ((uintptr_t)ws & 7) == 0, "depth_metrics: bad arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int g = red_grid(n);
-    double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(metrics_partial_kernel, dim3(g), dim3(256), 0, s, output, target, n, part);
-    RD_CHECK_LAUNCH("metrics_partial_kernel");
-    hipLaunchKernelGGL(pair_final_kernel, dim3(1), dim3(256), 0, s, part, g, 10, sums);
-    RD_CHECK_LAUNCH("pair_final_kernel");
-    return RD_OK;
+    return launch_sums<LOSS_NONE, true>(output, target, n, 0.0, ws, nullptr, sums, stream);
 }
 
 // Loss sums and metric sums in one pass over pred / target: sums[2] exactly as rd_masked_l1_sums / rd_masked_l2_sums write them,
 // msums[10] as rd_depth_metrics lists them.  ws: 12*rd_loss_tiles(n) doubles
-template <bool SQ>
-static int sums_metrics(const char* what, const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
-                        void* stream) {
-    RD_CHECK_ARG(pred && target && ws && sums && msums && n > 0 && ((uintptr_t)ws & 7) == 0, "%s: bad arguments", what);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int g = red_grid(n);
-    double* part = reinterpret_cast<double*>(ws);
-    hipLaunchKernelGGL(l1_metrics_partial_kernel<SQ>, dim3(g), dim3(256), 0, s, pred, target, n, part);
-    RD_CHECK_LAUNCH("l1_metrics_partial_kernel");
-    hipLaunchKernelGGL(split_final_kernel, dim3(1), dim3(256), 0, s, part, g, 2, 10, sums, msums);
-    RD_CHECK_LAUNCH("split_final_kernel");
-    return RD_OK;
-}
 extern "C" int rd_masked_l1_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
                                          void* stream) {
-    return sums_metrics<false>("masked_l1_sums_metrics", pred, target, n, ws, sums, msums, stream);
+    RD_CHECK_ARG(pred && target && ws && sums && msums && n > 0 && ((uintptr_t)ws & 7) == 0, "masked_l1_sums_metrics: bad arguments");
+    return launch_sums<LOSS_L1, true>(pred, target, n, 0.0, ws, sums, msums, stream);
 }
 extern "C" int rd_masked_l2_sums_metrics(const float* pred, const float* target, int64_t n, float* ws, double* sums, double* msums,
                                          void* stream) {
-    return sums_metrics<true>("masked_l2_sums_metrics", pred, target, n, ws, sums, msums, stream);
+    RD_CHECK_ARG(pred && target && ws && sums && msums && n > 0 && ((uintptr_t)ws & 7) == 0, "masked_l2_sums_metrics: bad arguments");
+    return launch_sums<LOSS_L2, true>(pred, target, n, 0.0, ws, sums, msums, stream);
 }
 
 // sums[frames][10]: the ten sums of rd_depth_metrics for every frame of a [frames,1,H,W] pair (hw = H*W); a frame without a valid
@@ -734,17 +618,7 @@ static int berhu_sums(const char* what, const float* pred, const float* target, 
     RD_CHECK_CODE(std::isfinite(thresh) && thresh > 0.0, RD_EBERHU_THRESH, "%s: thresh = %g has to be finite and positive", what, thresh);
     RD_CHECK_CODE((((uintptr_t)ws | (uintptr_t)sums | (uintptr_t)msums) & 7) == 0, RD_EBERHU_ALIGN,
                   "%s: the workspace and the sums have to be 8-byte aligned", what);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int g = red_grid(n);
-    double* part = reinterpret_cast<double*>(ws);
-    unsigned* pmax = reinterpret_cast<unsigned*>(part + (size_t)12 * g);
-    hipLaunchKernelGGL(berhu_max_kernel, dim3(g), dim3(256), 0, s, pred, target, n, pmax);
-    RD_CHECK_LAUNCH("berhu_max_kernel");
-    hipLaunchKernelGGL(berhu_partial_kernel<MET>, dim3(g), dim3(256), 0, s, pred, target, n, thresh, pmax, g, part);
-    RD_CHECK_LAUNCH("berhu_partial_kernel");
-    hipLaunchKernelGGL(berhu_final_kernel, dim3(1), dim3(256), 0, s, part, pmax, g, MET ? 10 : 0, thresh, sums, msums);
-    RD_CHECK_LAUNCH("berhu_final_kernel");
-    return RD_OK;
+    return launch_sums<LOSS_BERHU, MET>(pred, target, n, thresh, ws, sums, msums, stream);
 }
 extern "C" int rd_masked_berhu_sums(const float* pred, const float* target, int64_t n, double thresh, float* ws, double* sums, void* stream) {
     return berhu_sums<false>("masked_berhu_sums", pred, target, n, thresh, ws, sums, nullptr, stream);
