@@ -1,7 +1,7 @@
 // Error reporting, device info, hipGraph helpers of libradardepth_hip.
 #include <stdarg.h>
 
-#include "common.h"
+#include "conv_host.h"
 
 namespace rd {
 static thread_local char g_err[512] = "";
@@ -75,12 +75,9 @@ __global__ __launch_bounds__(256) void poison_lds_kernel(unsigned* sink, int wor
     if (sink && lds_words[(threadIdx.x * 97) % words] == 0u) sink[0] = 1;      // keep the stores alive
 }
 extern "C" int rd_debug_poison_lds(void* stream) {
-    static std::atomic<unsigned long long> attr_set{0};
     const int bytes = 160 * 1024 - 1024;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(poison_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    hipLaunchKernelGGL(poison_lds_kernel, dim3(rd::num_cus() * 4), dim3(256), bytes, static_cast<hipStream_t>(stream), (unsigned*)nullptr, bytes / 4);
-    RD_CHECK_LAUNCH("poison_lds_kernel");
-    return RD_OK;
+    return rd::launch_dyn_lds<poison_lds_kernel>("poison_lds_kernel", dim3(rd::num_cus() * 4), dim3(256), bytes, bytes, static_cast<hipStream_t>(stream),
+                                                 (unsigned*)nullptr, bytes / 4);
 }
 
 // Events for fork/join between the plan's streams (captured as graph edges under hipStreamBeginCapture)

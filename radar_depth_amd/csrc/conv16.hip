@@ -15,7 +15,7 @@
 // descriptor), optional residual addend, optional BatchNorm partial sums [tile][2][16] (tile index = blockIdx, n-major).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
 

@@ -14,7 +14,7 @@
 //     (conflict-free b128 reads at a 32-byte pitch: 31 KB of LDS, four workgroups per CU).
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
 

@@ -20,13 +20,11 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
 
@@ -871,40 +869,19 @@ static bool plan_gconv(const RdConvDesc& d, GconvPlan& best, bool allow_split = 
 
 template <int MT, int NT, int WM, int WN, int CKW, bool SWZ, bool PIPE, bool GRP = false, bool BNB = false>
 static int launch_cfg(const GconvArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gconv_kernel<MT, NT, WM, WN, CKW, SWZ, PIPE, GRP, BNB>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gconv_kernel");
-    return RD_OK;
+    return launch_dyn_lds<gconv_kernel<MT, NT, WM, WN, CKW, SWZ, PIPE, GRP, BNB>>("gconv_kernel", dim3(grid), dim3(256), lds, 160 * 1024, s, a);
 }
 
-static int validate_desc(const RdConvDesc* d) {
-    RD_CHECK_ARG(d != nullptr, "gconv: null descriptor");
-    RD_CHECK_ARG(d->n_phases >= 1 && d->n_phases <= RD_MAX_PHASES, "gconv: n_phases=%d", d->n_phases);
-    RD_CHECK_ARG(d->Cin % 16 == 0 && d->ldi % 4 == 0, "gconv: Cin=%d must be a multiple of 16, ldi=%d of 4", d->Cin, d->ldi);
-    RD_CHECK_ARG(d->Cout % 4 == 0, "gconv: Cout=%d must be a multiple of 4", d->Cout);
-    RD_CHECK_ARG((int64_t)d->Hi * d->Wi * d->ldi * 4 < (int64_t)0x80000000u, "gconv: one input image must stay below 2 GiB (32-bit buffer offsets)");
-    RD_CHECK_ARG(d->in_stride >= 1 && d->in_stride <= 2 && d->out_stride >= 1 && d->out_stride <= 2, "gconv: strides");
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        RD_CHECK_ARG(p.n_taps >= 1 && p.n_taps <= RD_MAX_TAPS, "gconv: phase %d has %d taps", i, p.n_taps);
-        RD_CHECK_ARG(p.lh >= 1 && p.lw >= 1, "gconv: empty phase %d", i);
-        for (int t = 0; t < p.n_taps; ++t)
-            RD_CHECK_ARG(p.dh[t] >= p.dh_min && p.dh[t] <= p.dh_max && p.dw[t] >= p.dw_min && p.dw[t] <= p.dw_max,
-                         "gconv: tap %d of phase %d outside its declared range", t, i);
-    }
+static int gconv_domain(const RdConvDesc& d) {
+    RD_CHECK_ARG(d.Cin % 16 == 0 && d.ldi % 4 == 0, "gconv: Cin=%d must be a multiple of 16, ldi=%d of 4", d.Cin, d.ldi);
+    RD_CHECK_ARG(d.Cout % 4 == 0, "gconv: Cout=%d must be a multiple of 4", d.Cout);
+    RD_CHECK_ARG((int64_t)d.Hi * d.Wi * d.ldi * 4 < (int64_t)0x80000000u, "gconv: one input image must stay below 2 GiB (32-bit buffer offsets)");
+    RD_CHECK_ARG(d.in_stride >= 1 && d.in_stride <= 2 && d.out_stride >= 1 && d.out_stride <= 2, "gconv: strides");
     return RD_OK;
 }
+static int validate_desc(const RdConvDesc* d) { return check_desc(d, "gconv", gconv_domain); }
 
-static void fill_tiles(RdConvDesc& d, GconvPlan& pl) {
-    int tb = 0;
-    for (int i = 0; i < d.n_phases; ++i) {
-        d.phase[i].tile_begin = tb;
-        tb += cdiv(d.phase[i].lh, pl.TH) * cdiv(d.phase[i].lw, pl.TW);
-    }
-    pl.tiles_total = tb;
-}
+static void fill_tiles(RdConvDesc& d, GconvPlan& pl) { pl.tiles_total = fill_tile_begin(d, pl.TH, pl.TW); }
 
 }  // namespace rd
 
@@ -956,21 +933,14 @@ extern "C" int rd_gconv_occupancy(const RdConvDesc* d) {
 // tile search (tens of microseconds) would otherwise be repeated on every one of them.
 struct PlanEntry { GconvPlan pl; RdConvDesc dd; int tuner_owned; };   // tuner_owned == 0: handed out by a plain query -- callers may
                                                                       // have sized buffers on it, so the tuner must not replace it
-static std::mutex g_plan_mu;
-static std::unordered_map<std::string, PlanEntry> g_plan_cache;
+static PlanCache<PlanEntry> g_plan_cache;
+// (generic: the fused -- bias / activation -- form of a conv16 descriptor on the 32x32 kernels)
+static std::string gconv_key(const RdConvDesc& d, bool allow_split, bool generic = false) { return plan_key(d, {allow_split ? 1 : 0, generic ? 1 : 0}); }
 static int plan_query(const RdConvDesc* d, bool allow_split, GconvPlan& pl, RdConvDesc& dd, bool generic_only) {
-    std::mutex& mu = g_plan_mu;
-    std::unordered_map<std::string, PlanEntry>& cache = g_plan_cache;
-    typedef PlanEntry Entry;
     RD_CHECK_ARG(d != nullptr, "gconv: null descriptor");
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(allow_split ? 1 : 0);
-    if (generic_only) key.push_back('g');      // the fused (bias / activation) form of a conv16 descriptor: 32x32 kernels
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(key);
-        if (it != cache.end()) { pl = it->second.pl; dd = it->second.dd; return RD_OK; }
-    }
+    std::string key = gconv_key(*d, allow_split, generic_only);
+    PlanEntry e;
+    if (g_plan_cache.find(key, e)) { pl = e.pl; dd = e.dd; return RD_OK; }
     int rc = validate_desc(d);
     if (rc != RD_OK) return rc;
     dd = *d;
@@ -983,8 +953,7 @@ static int plan_query(const RdConvDesc* d, bool allow_split, GconvPlan& pl, RdCo
         if (!plan_gconv(dd, pl, allow_split)) { set_error("gconv: no feasible tiling"); return RD_EINVAL; }
         fill_tiles(dd, pl);
     }
-    std::lock_guard<std::mutex> lk(mu);
-    cache.emplace(std::move(key), Entry{pl, dd, 0});
+    g_plan_cache.insert(std::move(key), PlanEntry{pl, dd, 0});
     return RD_OK;
 }
 
@@ -1002,11 +971,8 @@ extern "C" int rd_gconv_tune_candidates(const RdConvDesc* d, int32_t allow_split
     RD_CHECK_ARG(out && max_candidates > 0, "gconv_tune_candidates: bad arguments");
     if (conv16_eligible(*d)) return 0;          // one kernel, one tiling
     {   // a descriptor somebody already planned without the tuner keeps its plan (its buffers were sized on it): nothing to tune
-        std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-        key.push_back(allow_split ? 1 : 0);
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        auto it = g_plan_cache.find(key);
-        if (it != g_plan_cache.end() && !it->second.tuner_owned) return 0;
+        PlanEntry e;
+        if (g_plan_cache.find(gconv_key(*d, allow_split != 0), e) && !e.tuner_owned) return 0;
     }
     std::vector<std::pair<double, GconvPlan>> all;
     GconvPlan best;
@@ -1035,8 +1001,6 @@ extern "C" int rd_gconv_tune_candidates(const RdConvDesc* d, int32_t allow_split
 extern "C" int rd_gconv_tune_pin(const RdConvDesc* d, int32_t allow_split, const int32_t* cand) {
     if (validate_desc(d) != RD_OK) return RD_EINVAL;
     RD_CHECK_ARG(!conv16_eligible(*d), "gconv_tune_pin: descriptor is served by the conv16 kernel");
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(allow_split ? 1 : 0);
     GconvPlan pl;
     RdConvDesc dd = *d;
     if (!cand) {
@@ -1051,11 +1015,14 @@ extern "C" int rd_gconv_tune_pin(const RdConvDesc* d, int32_t allow_split, const
         RD_CHECK_ARG(found, "gconv_tune_pin: not a feasible plan of this descriptor");
     }
     fill_tiles(dd, pl);
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plan_cache.find(key);
-    RD_CHECK_ARG(it == g_plan_cache.end() || it->second.tuner_owned, "gconv_tune_pin: this descriptor is already planned and in use");
-    g_plan_cache[key] = PlanEntry{pl, dd, 1};
-    return RD_OK;
+    // (check and replace under one lock: a plan somebody uses is never swapped)
+    return g_plan_cache.locked([&](auto& cache) -> int {
+        const std::string key = gconv_key(*d, allow_split != 0);
+        auto it = cache.find(key);
+        RD_CHECK_ARG(it == cache.end() || it->second.tuner_owned, "gconv_tune_pin: this descriptor is already planned and in use");
+        cache[key] = PlanEntry{pl, dd, 1};
+        return RD_OK;
+    });
 }
 
 // A pinned plan is provisional (tuner_owned) until it is COMMITTED: callers commit right after their last pin for a descriptor and
@@ -1066,21 +1033,17 @@ extern "C" int rd_gconv_tune_commit(const RdConvDesc* d, int32_t allow_split) {
     GconvPlan pl; RdConvDesc dd;
     int rc = plan_query(d, allow_split != 0, pl, dd, false);
     if (rc != RD_OK) return rc;
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(allow_split ? 1 : 0);
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plan_cache.find(key);
-    if (it != g_plan_cache.end()) it->second.tuner_owned = 0;
+    g_plan_cache.locked([&](auto& cache) {
+        auto it = cache.find(gconv_key(*d, allow_split != 0));
+        if (it != cache.end()) it->second.tuner_owned = 0;
+    });
     return RD_OK;
 }
 // 0: not planned yet, 1: pinned by a tuner and still replaceable, 2: in use (heuristic plan handed out, or a committed pin)
 extern "C" int rd_gconv_plan_state(const RdConvDesc* d, int32_t allow_split) {
     if (!d) return RD_EINVAL;
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(allow_split ? 1 : 0);
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    auto it = g_plan_cache.find(key);
-    return it == g_plan_cache.end() ? 0 : it->second.tuner_owned ? 1 : 2;
+    PlanEntry e;
+    return !g_plan_cache.find(gconv_key(*d, allow_split != 0), e) ? 0 : e.tuner_owned ? 1 : 2;
 }
 
 // The plan a launch uses.  With a workspace: the split-allowed plan.  Without one: the split-allowed plan when it does not split
@@ -1113,13 +1076,9 @@ extern "C" int rd_gconv_stat_tiles_ws(const RdConvDesc* d) {
     return (int)((M + combine_rows_per_block(M) - 1) / combine_rows_per_block(M));
 }
 
-static unsigned long long* g_trace_buf = nullptr;
+static TraceBuf<64> g_trace;
 // diagnostics: copy the stamps of the last traced launch (64 per workgroup) to the host
-extern "C" int rd_gconv_trace_read(unsigned long long* host, int n_wg) {
-    if (!g_trace_buf) return RD_EINVAL;
-    RD_CHECK_HIP(hipMemcpy(host, g_trace_buf, (size_t)n_wg * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RD_OK;
-}
+extern "C" int rd_gconv_trace_read(unsigned long long* host, int n_wg) { return g_trace.read(host, n_wg); }
 
 struct BnBwdArgs { const float* x; int ld; const float* mean; const float* scale; const float* shift; int act; };
 
@@ -1190,12 +1149,7 @@ static int gconv_impl(const RdConvDesc* d, const float* in, const float* w_packe
     a.lds_floats = (int)((pl.lds_bytes + 7) / 8) * 2;
     {
         static const char* tr = getenv("RD_GCONV_TRACE");
-        if (tr && atoi(tr)) {
-            static unsigned long long* buf = nullptr;
-            if (!buf) RD_CHECK_HIP(hipMalloc(&buf, (size_t)65536 * 64 * sizeof(unsigned long long)));
-            g_trace_buf = buf;
-            a.trace = buf;
-        }
+        if (tr && atoi(tr) && (rc = g_trace.get(a.trace)) != RD_OK) return rc;
     }
     const int grid = d->N * pl.tiles_total * pl.n_cotiles * pl.ksplit;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -12,12 +12,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
 
@@ -558,47 +556,29 @@ static bool plan_gconv_bf16(const RdConvDesc& d, GconvBfPlan& best) {
 
 template <int MT, int NT, bool PIPE, bool IO16>
 static int launch_bf(const GconvBfArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gconv_bf16_kernel<MT, NT, PIPE, IO16>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gconv_bf16_kernel");
+    return launch_dyn_lds<gconv_bf16_kernel<MT, NT, PIPE, IO16>>("gconv_bf16_kernel", dim3(grid), dim3(256), lds, 160 * 1024, s, a);
+}
+
+static int bf_domain(const RdConvDesc& d) {
+    RD_CHECK_ARG(d.Cin % 16 == 0 && d.ldi % 4 == 0, "gconv_bf16: Cin=%d must be a multiple of 16, ldi=%d of 4", d.Cin, d.ldi);
+    RD_CHECK_ARG(d.in_stride >= 1 && d.in_stride <= 2 && d.out_stride >= 1 && d.out_stride <= 2, "gconv_bf16: strides");
+    RD_CHECK_ARG((int64_t)d.Hi * d.Wi * d.ldi * 4 < (int64_t)RD_OOB, "gconv_bf16: one input image must stay below 2 GiB (32-bit buffer offsets)");
     return RD_OK;
 }
 
 static int bf_plan_query(const RdConvDesc* d, GconvBfPlan& pl, RdConvDesc& dd) {
     struct Entry { GconvBfPlan pl; RdConvDesc dd; };
-    static std::mutex mu;
-    static std::unordered_map<std::string, Entry> cache;
+    static PlanCache<Entry> cache;
     RD_CHECK_ARG(d != nullptr, "gconv_bf16: null descriptor");
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(key);
-        if (it != cache.end()) { pl = it->second.pl; dd = it->second.dd; return RD_OK; }
-    }
-    RD_CHECK_ARG(d->n_phases >= 1 && d->n_phases <= RD_MAX_PHASES, "gconv_bf16: n_phases=%d", d->n_phases);
-    RD_CHECK_ARG(d->Cin % 16 == 0 && d->ldi % 4 == 0, "gconv_bf16: Cin=%d must be a multiple of 16, ldi=%d of 4", d->Cin, d->ldi);
-    RD_CHECK_ARG(d->in_stride >= 1 && d->in_stride <= 2 && d->out_stride >= 1 && d->out_stride <= 2, "gconv_bf16: strides");
-    RD_CHECK_ARG((int64_t)d->Hi * d->Wi * d->ldi * 4 < (int64_t)RD_OOB, "gconv_bf16: one input image must stay below 2 GiB (32-bit buffer offsets)");
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        RD_CHECK_ARG(p.n_taps >= 1 && p.n_taps <= RD_MAX_TAPS, "gconv_bf16: phase %d has %d taps", i, p.n_taps);
-        RD_CHECK_ARG(p.lh >= 1 && p.lw >= 1, "gconv_bf16: empty phase %d", i);
-        for (int t = 0; t < p.n_taps; ++t)
-            RD_CHECK_ARG(p.dh[t] >= p.dh_min && p.dh[t] <= p.dh_max && p.dw[t] >= p.dw_min && p.dw[t] <= p.dw_max,
-                         "gconv_bf16: tap %d of phase %d outside its declared range", t, i);
-    }
+    std::string key = plan_key(*d);
+    Entry e;
+    if (cache.find(key, e)) { pl = e.pl; dd = e.dd; return RD_OK; }
+    const int rc = check_desc(d, "gconv_bf16", bf_domain);
+    if (rc != RD_OK) return rc;
     dd = *d;
     if (!plan_gconv_bf16(dd, pl)) { set_error("gconv_bf16: no feasible tiling"); return RD_EINVAL; }
-    int tb = 0;
-    for (int i = 0; i < dd.n_phases; ++i) {
-        dd.phase[i].tile_begin = tb;
-        tb += cdiv(dd.phase[i].lh, pl.TH) * cdiv(dd.phase[i].lw, pl.TW);
-    }
-    pl.tiles_total = tb;
-    std::lock_guard<std::mutex> lk(mu);
-    cache.emplace(std::move(key), Entry{pl, dd});
+    pl.tiles_total = fill_tile_begin(dd, pl.TH, pl.TW);
+    cache.insert(std::move(key), Entry{pl, dd});
     return RD_OK;
 }
 
@@ -606,13 +586,9 @@ static int bf_plan_query(const RdConvDesc* d, GconvBfPlan& pl, RdConvDesc& dd) {
 
 using namespace rd;
 
-static unsigned long long* g_bf_trace = nullptr;
+static TraceBuf<32> g_bf_trace;
 // diagnostics: copy the stamps of the last traced launch (32 slots per workgroup: count, then cycle-counter values)
-extern "C" int rd_gconv_bf16_trace_read(unsigned long long* host, int n_wg) {
-    if (!g_bf_trace) return RD_EINVAL;
-    RD_CHECK_HIP(hipMemcpy(host, g_bf_trace, (size_t)n_wg * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RD_OK;
-}
+extern "C" int rd_gconv_bf16_trace_read(unsigned long long* host, int n_wg) { return g_bf_trace.read(host, n_wg); }
 
 extern "C" int rd_gconv_bf16_plan_info(const RdConvDesc* d, int32_t* out) {
     GconvBfPlan pl; RdConvDesc dd;
@@ -664,11 +640,8 @@ static int gconv_bf16_impl(bool io16, const RdConvDesc* d, const void* in, const
     a.TH = pl.TH; a.TW = pl.TW; a.PP = pl.PP; a.CKP = pl.CKP;
     a.tiles_total = pl.tiles_total; a.n_cotiles = pl.n_cotiles; a.taps_max = pl.taps_max;
     {
-        const uintptr_t al = io16 ? 8 : 16;     // four channels
         static const char* novec = getenv("RD_GCONV_BF16_NOVEC4");   // diagnostics: element-wise epilogue
-        a.vec4 = !novec && d->Cout % 4 == 0 && d->ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % al == 0 && act_cols % 4 == 0 &&
-                 (!addend || (ld_add % 4 == 0 && reinterpret_cast<uintptr_t>(addend) % al == 0)) &&
-                 (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
+        a.vec4 = !novec && epilogue_vec4_ok(out, d->ldo, d->Cout, act_cols, addend, ld_add, bias, io16 ? 2 : 4);
     }
     const int PSB = (pl.CKP + 8) * 2;
     for (int i = 0; i < d->n_phases; ++i) {
@@ -681,10 +654,7 @@ static int gconv_bf16_impl(bool io16, const RdConvDesc* d, const void* in, const
     a.trace = nullptr;
     {
         static const char* tr = getenv("RD_GCONV_BF16_TRACE");
-        if (tr && atoi(tr)) {
-            if (!g_bf_trace) RD_CHECK_HIP(hipMalloc(&g_bf_trace, (size_t)65536 * 32 * sizeof(unsigned long long)));
-            a.trace = g_bf_trace;
-        }
+        if (tr && atoi(tr) && (rc = g_bf_trace.get(a.trace)) != RD_OK) return rc;
     }
 #define RD_BF(MT_, NT_)                                                                                                        \
     if (pl.MT == MT_ && pl.NT == NT_)                                                                                          \

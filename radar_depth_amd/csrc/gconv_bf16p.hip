@@ -28,13 +28,11 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 #include "slot_map.h"
 
 namespace rd {
@@ -447,18 +445,12 @@ struct GpPlan {
 };
 
 static bool gp_shape_ok(const RdConvDesc* d) {
-    if (!d || d->n_phases < 1 || d->n_phases > RD_MAX_PHASES) return false;
+    if (!d || !desc_taps_ok(*d, 9)) return false;
     if (d->in_stride != 1 || d->out_stride < 1 || d->out_stride > 2) return false;
     if (d->Cin % 16 != 0 || d->Cin < 32 || d->ldi % 8 != 0 || d->Cout % 32 != 0) return false;
     if ((int64_t)d->Hi * d->Wi * d->ldi * 2 >= (int64_t)GP_OOB) return false;
     int taps_max = 0;
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        if (p.n_taps < 1 || p.n_taps > 9 || p.lh < 1 || p.lw < 1) return false;
-        taps_max = taps_max > p.n_taps ? taps_max : p.n_taps;
-        for (int t = 0; t < p.n_taps; ++t)
-            if (p.dh[t] < p.dh_min || p.dh[t] > p.dh_max || p.dw[t] < p.dw_min || p.dw[t] > p.dw_max) return false;
-    }
+    for (int i = 0; i < d->n_phases; ++i) taps_max = taps_max > d->phase[i].n_taps ? taps_max : d->phase[i].n_taps;
     if (taps_max < 4) return false;          // 1x1 layers: a stage would be four MFMAs
     return true;
 }
@@ -524,32 +516,19 @@ static bool plan_bf16p(const RdConvDesc& d, GpPlan& pl) {
     return best > 0;
 }
 
-static std::mutex g_gp_mu;
-static int g_gp_all = -1;          // -1: not set yet (RD_GCONV_BF16P=all decides at first use)
-static unsigned g_gp_epoch = 0;    // bumped by gconv_bf16p_plan_all: plans cached under the other setting are dropped
+// rd_gconv_bf16p_plan_all / RD_GCONV_BF16P=all
+static PlanAllSwitch g_gp_all([]() { return getenv("RD_GCONV_BF16P") && getenv("RD_GCONV_BF16P")[0] == 'a'; });
 
 static int gp_plan_query(const RdConvDesc* d, GpPlan& pl, RdConvDesc& dd) {
     struct Entry { int ok; GpPlan pl; RdConvDesc dd; };
-    static std::mutex mu;
-    static std::unordered_map<std::string, Entry> cache;
-    static unsigned cache_epoch = 0;
+    static PlanCache<Entry> cache;
     if (!d) return 0;
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    bool all;
-    {
-        unsigned ep;
-        {
-            std::lock_guard<std::mutex> lk(g_gp_mu);
-            if (g_gp_all < 0) g_gp_all = (getenv("RD_GCONV_BF16P") && getenv("RD_GCONV_BF16P")[0] == 'a') ? 1 : 0;
-            all = g_gp_all == 1;
-            ep = g_gp_epoch;
-        }
-        std::lock_guard<std::mutex> lk(mu);
-        if (ep != cache_epoch) { cache.clear(); cache_epoch = ep; }
-        auto it = cache.find(key);
-        if (it != cache.end()) { pl = it->second.pl; dd = it->second.dd; return it->second.ok; }
-    }
-    Entry e{};
+    std::string key = plan_key(*d);
+    unsigned ep;
+    const bool all = g_gp_all.get(&ep);
+    Entry e;
+    if (cache.find(key, e, ep)) { pl = e.pl; dd = e.dd; return e.ok; }
+    e = Entry{};
     e.dd = *d;
     static const bool off = getenv("RD_GCONV_BF16P") && atoi(getenv("RD_GCONV_BF16P")) == 0;      // A/B switch: everything on gconv_bf16_kernel
     e.ok = !off && gp_shape_ok(d) && plan_bf16p(e.dd, e.pl) ? 1 : 0;
@@ -563,24 +542,16 @@ static int gp_plan_query(const RdConvDesc* d, GpPlan& pl, RdConvDesc& dd) {
         for (int i = 0; i < e.dd.n_phases; ++i) tb0 += cdiv(e.dd.phase[i].lh, e.pl.TH) * cdiv(e.dd.phase[i].lw, e.pl.TW);
         if (!all && !(e.pl.MT == 2 && (int64_t)d->N * tb0 * e.pl.n_cotiles >= 4 * (int64_t)num_cus())) e.ok = 0;
     }
-    if (e.ok) {
-        int tb = 0;
-        for (int i = 0; i < e.dd.n_phases; ++i) {
-            e.dd.phase[i].tile_begin = tb;
-            tb += cdiv(e.dd.phase[i].lh, e.pl.TH) * cdiv(e.dd.phase[i].lw, e.pl.TW);
-        }
-        e.pl.tiles_total = tb;
-    }
+    if (e.ok) e.pl.tiles_total = fill_tile_begin(e.dd, e.pl.TH, e.pl.TW);
     pl = e.pl; dd = e.dd;
-    std::lock_guard<std::mutex> lk(mu);
-    cache.emplace(std::move(key), e);
+    cache.insert(std::move(key), e);
     return e.ok;
 }
 
 // slot table of a plan on the current device (see gs_slot_table in gconv_split.hip); keyed by the tile alone
 static const int* gp_slot_table(const GpPlan& pl) {
     static std::mutex mu;
-    static std::unordered_map<uint64_t, int*> tables;
+    static std::unordered_map<uint64_t, const int*> tables;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     const uint64_t key = ((uint64_t)dev << 56) | ((uint64_t)pl.MT << 48) | ((uint64_t)pl.rowp << 32) | ((uint64_t)pl.TH << 16) | (uint64_t)pl.TW;
@@ -593,32 +564,19 @@ static const int* gp_slot_table(const GpPlan& pl) {
         int r, c, rho;
         host[m] = gs_slot_pixel(m, pl.TH, pl.TW, pl.rowp, BM / 16, pl.nres, false, r, c, rho) ? ((r << 16) | c) : -1 - rho;
     }
-    int* devp = nullptr;
-    if (hipMalloc(&devp, host.size() * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemcpy(devp, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(devp); return nullptr; }
-    tables.emplace(key, devp);
+    const int* devp = upload_slot_table(host);
+    if (devp) tables.emplace(key, devp);
     return devp;
 }
 
 template <int MT, int NT, int DBG = 0>
 static int launch_gp(const GpArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gconv_bf16p_kernel<MT, NT, DBG>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gconv_bf16p_kernel");
-    return RD_OK;
+    return launch_dyn_lds<gconv_bf16p_kernel<MT, NT, DBG>>("gconv_bf16p_kernel", dim3(grid), dim3(256), lds, 80 * 1024, s, a);
 }
 
 // tests / sweeps: on != 0 serves every shape the kernel can run, also those the planner rule leaves to gconv_bf16_kernel; returns the
 // previous setting.  Do not toggle between sizing a statistics buffer on a plan and launching it.
-int gconv_bf16p_plan_all(int on) {
-    std::lock_guard<std::mutex> lk(g_gp_mu);
-    if (g_gp_all < 0) g_gp_all = (getenv("RD_GCONV_BF16P") && getenv("RD_GCONV_BF16P")[0] == 'a') ? 1 : 0;
-    const int prev = g_gp_all;
-    if ((on != 0) != (prev == 1)) { g_gp_all = on ? 1 : 0; ++g_gp_epoch; }
-    return prev;
-}
+int gconv_bf16p_plan_all(int on) { return g_gp_all.set(on); }
 
 // 1 when the persistent kernel serves d with bf16 tensors (rd_gconv_bf16_t dispatches to it; its statistics tiling is its own)
 int gconv_bf16p_supported(const RdConvDesc* d) {
@@ -653,8 +611,7 @@ int launch_gconv_bf16p(const RdConvDesc* d, const void* in, const void* w_packed
     a.TH = pl.TH; a.TW = pl.TW; a.tiles_total = pl.tiles_total; a.n_cotiles = pl.n_cotiles; a.taps_max = pl.taps_max;
     a.njobs = d->N * pl.tiles_total * pl.n_cotiles;
     a.wslot = pl.wslot; a.pslot = pl.pslot; a.rowb = pl.rowp * 16;
-    a.vec4 = d->ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 8 == 0 && act_cols % 4 == 0 &&
-             (!addend || (ld_add % 4 == 0 && reinterpret_cast<uintptr_t>(addend) % 8 == 0)) && (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
+    a.vec4 = epilogue_vec4_ok(out, d->ldo, d->Cout, act_cols, addend, ld_add, bias, 2);      // (Cout % 32 == 0 holds: gp_shape_ok)
     for (int i = 0; i < d->n_phases; ++i) {
         const RdPhase& p = d->phase[i];
         for (int t = 0; t < p.n_taps; ++t) a.tapoff[i][t] = (p.dh[t] - p.dh_min) * a.rowb + (p.dw[t] - p.dw_min) * 16;

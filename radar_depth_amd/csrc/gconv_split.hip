@@ -28,13 +28,11 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 #include "slot_map.h"
 
 namespace rd {
@@ -1474,39 +1472,23 @@ static bool plan_sp2(const RdConvDesc& d, GsPlan& best) {
 
 template <int MT, int NT, int DBG = 0, bool BNB = false>
 static int launch_sp2(const GsArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gconv_sp2_kernel<MT, NT, DBG, BNB>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gconv_sp2_kernel");
-    return RD_OK;
+    return launch_dyn_lds<gconv_sp2_kernel<MT, NT, DBG, BNB>>("gconv_sp2_kernel", dim3(grid), dim3(256), lds, 80 * 1024, s, a);
 }
 
 template <int MT, int NT, bool PDB, bool PRE, bool BNB = false>
 static int launch_gs(const GsArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gconv_split_kernel<MT, NT, PDB, PRE, BNB>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, a);
-    RD_CHECK_LAUNCH("gconv_split_kernel");
-    return RD_OK;
+    return launch_dyn_lds<gconv_split_kernel<MT, NT, PDB, PRE, BNB>>("gconv_split_kernel", dim3(grid), dim3(512), lds, 160 * 1024, s, a);
 }
 
-static std::mutex g_gs_mu;
-static int g_gs_all = -1;         // -1: not set yet (the environment decides at first use)
-static unsigned g_gs_epoch = 0;   // bumped by rd_gconv_split_plan_all: plans cached under another setting are dropped
-static bool gs_plan_all() {
-    std::lock_guard<std::mutex> lk(g_gs_mu);
-    if (g_gs_all < 0) g_gs_all = getenv("RD_GCONV_SPLIT_ALL") ? 1 : 0;
-    return g_gs_all == 1;
-}
+// rd_gconv_split_plan_all / RD_GCONV_SPLIT_ALL
+static PlanAllSwitch g_gs_all([]() { return getenv("RD_GCONV_SPLIT_ALL") != nullptr; });
 
 static bool gs_shape_ok(const RdConvDesc* d, bool sp2 = false) {
-    if (!d || d->n_phases < 1 || d->n_phases > RD_MAX_PHASES) return false;
+    if (!d || !desc_taps_ok(*d)) return false;
     if (d->Cin % 16 != 0 || d->ldi % 4 != 0 || d->Cin < 32 || d->Cout < 32) return false;      // (the 16-channel layers stay on conv16.hip)
     if (d->in_stride < 1 || d->in_stride > 2 || d->out_stride < 1 || d->out_stride > 2) return false;
     // (rd_gconv_split_plan_all(1), tests: plan every shape the kernel can run; RD_GCONV_SPLIT_ALL=1 sets the initial value)
-    if (!gs_plan_all()) {
+    if (!g_gs_all.get()) {
         // measured slower than (or level with) gconv.hip at the bench geometry (tools/bench_split.py, profiles/r03_bench_split.txt):
         //   * one-tap layers (0.4-0.8x: a chunk is 36 MFMAs, nothing to hide the staging behind);
         //   * fewer than 64 channels on a side (0.8-1.0x on the 32-channel decoder layers: the 32-wide output tile halves the reuse
@@ -1525,50 +1507,30 @@ static bool gs_shape_ok(const RdConvDesc* d, bool sp2 = false) {
         if (d->in_stride == 2 && taps_max <= 9 && !(sp2 && s2pre >= 1)) return false;
         if (d->out_stride == 2 && taps_max <= 4 && !(sp2 && s2pre >= 2)) return false;      // stride-2 input gradient (phases of 1 / 2 / 2 / 4 taps)
     }
-    if ((int64_t)d->Hi * d->Wi * d->ldi * 4 >= (int64_t)GS_OOB) return false;
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        if (p.n_taps < 1 || p.n_taps > RD_MAX_TAPS || p.lh < 1 || p.lw < 1) return false;
-        for (int t = 0; t < p.n_taps; ++t)
-            if (p.dh[t] < p.dh_min || p.dh[t] > p.dh_max || p.dw[t] < p.dw_min || p.dw[t] > p.dw_max) return false;
-    }
-    return true;
+    return (int64_t)d->Hi * d->Wi * d->ldi * 4 < (int64_t)GS_OOB;
 }
 
 // 1: planned, 0: no plan (shape outside the kernel's domain or no tiling fits the LDS)
 static int gs_plan_query(const RdConvDesc* d, GsPlan& pl, RdConvDesc& dd, bool pre = false) {
     struct Entry { int ok; GsPlan pl; RdConvDesc dd; };
-    static std::mutex mu;
-    static std::unordered_map<std::string, Entry> cache;
-    static unsigned cache_epoch = 0;
+    static PlanCache<Entry> cache;
     if (!d) return 0;
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(pre ? 'P' : 'R');
-    {
-        unsigned ep;
-        { std::lock_guard<std::mutex> lk(g_gs_mu); ep = g_gs_epoch; }
-        std::lock_guard<std::mutex> lk(mu);
-        if (ep != cache_epoch) { cache.clear(); cache_epoch = ep; }
-        auto it = cache.find(key);
-        if (it != cache.end()) { pl = it->second.pl; dd = it->second.dd; return it->second.ok; }
-    }
-    Entry e{};
+    std::string key = plan_key(*d, {pre ? 1 : 0});
+    unsigned ep;
+    g_gs_all.get(&ep);
+    Entry e;
+    if (cache.find(key, e, ep)) { pl = e.pl; dd = e.dd; return e.ok; }
+    e = Entry{};
     e.dd = *d;
     static const char* no_sp2 = getenv("RD_GCONV_SP2");          // RD_GCONV_SP2=0: pre-split input on the 8-wave kernel (diagnostics)
     const bool sp2 = pre && !(no_sp2 && atoi(no_sp2) == 0);
     e.ok = gs_shape_ok(d, sp2) && (sp2 ? plan_sp2(e.dd, e.pl) : plan_gconv_split(e.dd, e.pl, pre)) ? 1 : 0;
     if (e.ok) {
-        int tb = 0;
-        for (int i = 0; i < e.dd.n_phases; ++i) {
-            e.dd.phase[i].tile_begin = tb;
-            tb += cdiv(e.dd.phase[i].lh, e.pl.TH) * cdiv(e.dd.phase[i].lw, e.pl.TW);
-        }
-        e.pl.tiles_total = tb;
+        e.pl.tiles_total = fill_tile_begin(e.dd, e.pl.TH, e.pl.TW);
         gs_fill_slot_map(e.dd, e.pl);
     }
     pl = e.pl; dd = e.dd;
-    std::lock_guard<std::mutex> lk(mu);
-    cache.emplace(std::move(key), e);
+    cache.insert(std::move(key), e);
     return e.ok;
 }
 
@@ -1577,16 +1539,13 @@ static int gs_plan_query(const RdConvDesc* d, GsPlan& pl, RdConvDesc& dd, bool p
 // never freed (a few KB per distinct descriptor); RD_GCONV_SPLIT_NATURAL=1 (diagnostics, read once): the round-4 row-major map.
 static const int* gs_slot_table(const RdConvDesc* d, bool pre, const GsPlan& pl) {
     static std::mutex mu;
-    static std::unordered_map<std::string, int*> tables;
+    static std::unordered_map<std::string, const int*> tables;
     static const bool natural = getenv("RD_GCONV_SPLIT_NATURAL") && atoi(getenv("RD_GCONV_SPLIT_NATURAL"));
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     unsigned ep;
-    { std::lock_guard<std::mutex> lk(g_gs_mu); ep = g_gs_epoch; }
-    std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    key.push_back(pre ? 'P' : 'R');
-    key.append(reinterpret_cast<const char*>(&dev), sizeof(dev));
-    key.append(reinterpret_cast<const char*>(&ep), sizeof(ep));
+    g_gs_all.get(&ep);
+    std::string key = plan_key(*d, {pre ? 1 : 0, dev, (int)ep});
     std::lock_guard<std::mutex> lk(mu);
     auto it = tables.find(key);
     if (it != tables.end()) return it->second;
@@ -1598,10 +1557,8 @@ static const int* gs_slot_table(const RdConvDesc* d, bool pre, const GsPlan& pl)
             const bool have = gs_slot_pixel(m, pl.TH, pl.TW, pl.ppitch[i], BM / 16, pl.nres[i], natural, r, c, rho);
             host[(size_t)i * BM + m] = have ? ((r << 16) | c) : -1 - rho;
         }
-    int* devp = nullptr;
-    if (hipMalloc(&devp, host.size() * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemcpy(devp, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(devp); return nullptr; }
-    tables.emplace(std::move(key), devp);
+    const int* devp = upload_slot_table(host);
+    if (devp) tables.emplace(std::move(key), devp);
     return devp;
 }
 
@@ -1609,25 +1566,15 @@ static const int* gs_slot_table(const RdConvDesc* d, bool pre, const GsPlan& pl)
 
 using namespace rd;
 
-static unsigned long long* g_gs_trace = nullptr;
+static TraceBuf<64> g_gs_trace;
 // diagnostics: copy the stamps of the last traced launch (64 slots per workgroup: before / after barrier B1 of the first 30 tap
 // groups; [60] end of the MFMA loop, [61] end of the epilogue, [62] kernel entry, [63] tap groups)
-extern "C" int rd_gconv_split_trace_read(unsigned long long* host, int n_wg) {
-    if (!g_gs_trace) return RD_EINVAL;
-    RD_CHECK_HIP(hipMemcpy(host, g_gs_trace, (size_t)n_wg * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RD_OK;
-}
+extern "C" int rd_gconv_split_trace_read(unsigned long long* host, int n_wg) { return g_gs_trace.read(host, n_wg); }
 
 // tests / sweeps: on != 0 plans every shape the kernel can run, also those the library leaves to rd_gconv because they measured
 // slower there.  Returns the previous setting.  Plans cached under the other setting are dropped; callers that sized buffers on a
 // plan (statistics tiles) must not toggle this between the query and the launch.
-extern "C" int rd_gconv_split_plan_all(int on) {
-    gs_plan_all();
-    std::lock_guard<std::mutex> lk(g_gs_mu);
-    const int prev = g_gs_all;
-    if ((on != 0) != (prev == 1)) { g_gs_all = on ? 1 : 0; ++g_gs_epoch; }
-    return prev;
-}
+extern "C" int rd_gconv_split_plan_all(int on) { return g_gs_all.set(on); }
 
 // (one-tap descriptors -- 1x1 convolutions and their input gradients -- go to gemm1_split.hip's channel-grouped kernel: same operands,
 //  same arithmetic, same epilogue; the three queries below and rd_gconv_split answer for whichever kernel serves the descriptor)
@@ -1703,15 +1650,11 @@ static int gs_launch(const RdConvDesc* d, const float* in, const void* in_pieces
     a.kplane = pl.pplane / 2;
     if (pre) RD_CHECK_ARG(in_piece_elems >= (int64_t)(d->Cin / 16) * a.mpix * 16 && in_piece_elems % 8 == 0, "gconv_split: activation piece stride %lld too small for %d x %lld",
                           (long long)in_piece_elems, d->Cin, a.mpix);
-    int S = 0;
-    for (int i = 0; i < d->n_phases; ++i)
-        for (int t = 0; t < d->phase[i].n_taps; ++t) S = S > d->phase[i].widx[t] + 1 ? S : d->phase[i].widx[t] + 1;
+    const int S = weight_slabs(*d);
     RD_CHECK_ARG(piece_elems >= (int64_t)S * d->Cin * d->Cout && piece_elems % 8 == 0, "gconv_split: piece stride %lld too small for %d slabs of %d x %d",
                  (long long)piece_elems, S, d->Cin, d->Cout);
     a.wplane = (long long)piece_elems * 2;
-    a.vec4 = d->Cout % 4 == 0 && d->ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && act_cols % 4 == 0 &&
-             (!addend || (ld_add % 4 == 0 && reinterpret_cast<uintptr_t>(addend) % 16 == 0)) &&
-             (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
+    a.vec4 = epilogue_vec4_ok(out, d->ldo, d->Cout, act_cols, addend, ld_add, bias, 4);
     for (int i = 0; i < d->n_phases; ++i) {
         const RdPhase& p = d->phase[i];
         const int PW_ = pl.ppitch[i];
@@ -1740,8 +1683,8 @@ static int gs_launch(const RdConvDesc* d, const float* in, const void* in_pieces
     {
         static const char* tr = getenv("RD_GCONV_SPLIT_TRACE");
         if (tr && atoi(tr)) {
-            if (!g_gs_trace) RD_CHECK_HIP(hipMalloc(&g_gs_trace, (size_t)65536 * 64 * sizeof(unsigned long long)));
-            a.trace = g_gs_trace;
+            const int rc = g_gs_trace.get(a.trace);
+            if (rc != RD_OK) return rc;
             a.trace_role = atoi(tr);
         }
     }

@@ -20,7 +20,8 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_internal.h"
+#include "gemm_rows_host.h"
 
 namespace rd {
 
@@ -347,88 +348,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct G1Plan { int MT, NT, n_cotiles, tiles; int tile_begin[RD_MAX_PHASES + 1]; size_t lds; };
-
-static bool g1_plan(const RdConvDesc* d, G1Plan& pl) {
-    static const bool off = getenv("RD_GEMM1_SPLIT") && atoi(getenv("RD_GEMM1_SPLIT")) == 0;      // A/B switch: 1x1 layers stay on rd_gconv
-    if (off || !d || d->n_phases < 1 || d->n_phases > RD_MAX_PHASES) return false;
-    if (d->in_stride < 1 || d->in_stride > 2 || d->out_stride < 1 || d->out_stride > 2) return false;
-    if (d->Cin % G1_CK != 0 || d->Cin < 32 || d->Cout < 32 || d->Cout % 8 != 0 || d->ldi % 4 != 0) return false;
-    if ((int64_t)d->N * d->Hi * d->Wi * d->ldi / 2 >= (int64_t)G1_OOB) return false;
-    int64_t rows = 0;
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        if (p.n_taps != 1 || p.lh < 1 || p.lw < 1 || p.widx[0] < 0) return false;
-        rows += (int64_t)d->N * p.lh * p.lw;
+struct G1Host {
+    typedef G1Args Args;
+    static constexpr const char* name = "gemm1_split";
+    static constexpr int CK = G1_CK, MAX_TAPS = 1;
+    static bool enabled() {
+        static const bool off = getenv("RD_GEMM1_SPLIT") && atoi(getenv("RD_GEMM1_SPLIT")) == 0;      // A/B switch: 1x1 layers stay on rd_gconv
+        return !off;
     }
-    pl.NT = d->Cout > 32 ? 2 : 1;
-    if (d->Cout % (pl.NT * 32) != 0) return false;        // (the weight copies read whole column tiles)
-    pl.n_cotiles = d->Cout / (pl.NT * 32);
-    // 256-row tiles when they still give every CU its two workgroups, else 128-row tiles
-    pl.MT = (rows / 256) * pl.n_cotiles >= 2 * (int64_t)num_cus() ? 2 : 1;
-    const int BM = 4 * pl.MT * 32, BN = pl.NT * 32;
-    int tb = 0;
-    for (int i = 0; i < d->n_phases; ++i) {
-        pl.tile_begin[i] = tb;
-        tb += (int)cdiv64((int64_t)d->N * d->phase[i].lh * d->phase[i].lw, BM);
+    static int nt(int Cout) { return Cout > 32 ? 2 : 1; }
+    static size_t lds(int BM, int BN) { return (size_t)BM * 8 + 8 * BN * 4 + 3 * (size_t)4 * (BM * 16 + G1_UPAD) + 2 * 3 * (size_t)4 * BN * 16; }
+    static int marker(const RdConvDesc&) { return 1000; }      // (marks the 1x1 kernel in rd_gconv_split_plan_info)
+    template <int MT, int NT>
+    static int launch(const G1Args& a, int grid, size_t lds, hipStream_t s) {
+        return launch_dyn_lds<gemm1_split_kernel<MT, NT>>("gemm1_split_kernel", dim3(grid), dim3(256), lds, 80 * 1024, s, a);
     }
-    for (int i = d->n_phases; i <= RD_MAX_PHASES; ++i) pl.tile_begin[i] = tb;
-    pl.tiles = tb;
-    pl.lds = (size_t)BM * 8 + 8 * BN * 4 + 3 * (size_t)4 * (BM * 16 + G1_UPAD) + 2 * 3 * (size_t)4 * BN * 16;
-    return pl.lds <= 80 * 1024 - 256;
-}
+};
 
-template <int MT, int NT>
-static int launch_g1(const G1Args& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gemm1_split_kernel<MT, NT>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gemm1_split_kernel");
-    return RD_OK;
-}
-
-int gemm1_split_supported(const RdConvDesc* d) {
-    G1Plan pl;
-    return g1_plan(d, pl) ? 1 : 0;
-}
-
-int gemm1_split_stat_tiles(const RdConvDesc* d) {
-    G1Plan pl;
-    return g1_plan(d, pl) ? pl.tiles : RD_EINVAL;
-}
-
-int gemm1_split_plan_info(const RdConvDesc* d, int32_t* out) {
-    G1Plan pl;
-    if (!out || !g1_plan(d, pl)) return RD_EINVAL;
-    const int v[8] = {pl.MT, pl.NT, 4 * pl.MT * 32, 1, 0, (int)pl.lds, pl.tiles * pl.n_cotiles, 1000};
-    for (int i = 0; i < 8; ++i) out[i] = v[i];
-    return RD_OK;
-}
-
+int gemm1_split_supported(const RdConvDesc* d) { return row_gemm_supported<G1Host>(d); }
+int gemm1_split_stat_tiles(const RdConvDesc* d) { return row_gemm_stat_tiles<G1Host>(d); }
+int gemm1_split_plan_info(const RdConvDesc* d, int32_t* out) { return row_gemm_plan_info<G1Host>(d, out); }
 int launch_gemm1_split(const RdConvDesc* d, const float* in, const void* w_split, int64_t piece_elems, float* out, const float* bias, int32_t act,
                        int32_t act_cols, const float* addend, int32_t ld_add, float* stat_partial, hipStream_t s) {
-    G1Args a;
-    G1Plan pl;
-    if (!g1_plan(d, pl)) { set_error("gemm1_split: descriptor not supported"); return RD_EINVAL; }
-    RD_CHECK_ARG(in && w_split && out, "gemm1_split: null argument");
-    RD_CHECK_ARG(reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(w_split) % 16 == 0, "gemm1_split: unaligned tensor");
-    int S = 0;
-    for (int i = 0; i < d->n_phases; ++i) S = S > d->phase[i].widx[0] + 1 ? S : d->phase[i].widx[0] + 1;
-    RD_CHECK_ARG(piece_elems >= (int64_t)S * d->Cin * d->Cout && piece_elems % 8 == 0, "gemm1_split: piece stride %lld too small", (long long)piece_elems);
-    a.d = *d;
-    a.in = in; a.w = static_cast<const unsigned short*>(w_split); a.out = out; a.addend = addend; a.bias = bias; a.stat = stat_partial;
-    a.act = act; a.act_cols = act_cols; a.ld_add = ld_add; a.ldw = d->Cout;
-    a.n_cotiles = pl.n_cotiles;
-    a.wplane = (long long)piece_elems * 2;
-    a.vec4 = d->Cout % 4 == 0 && d->ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && act_cols % 4 == 0 &&
-             (!addend || (ld_add % 4 == 0 && reinterpret_cast<uintptr_t>(addend) % 16 == 0)) && (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
-    for (int i = 0; i <= RD_MAX_PHASES; ++i) a.tile_begin[i] = pl.tile_begin[i];
-    const int grid = pl.tiles * pl.n_cotiles;
-    if (pl.MT == 2 && pl.NT == 2) return launch_g1<2, 2>(a, grid, pl.lds, s);
-    if (pl.MT == 1 && pl.NT == 2) return launch_g1<1, 2>(a, grid, pl.lds, s);
-    if (pl.MT == 2 && pl.NT == 1) return launch_g1<2, 1>(a, grid, pl.lds, s);
-    return launch_g1<1, 1>(a, grid, pl.lds, s);
+    return row_gemm_launch<G1Host>(d, in, w_split, piece_elems, out, bias, act, act_cols, addend, ld_add, stat_partial, s);
 }
 
 }  // namespace rd

@@ -12,7 +12,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "gemm_rows_host.h"
 
 namespace rd {
 
@@ -342,109 +342,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void g
 }
 
 // ------------------------------------------------------------------------------------------ host
-struct GTPlan { int MT, NT, n_cotiles, tiles; int tile_begin[RD_MAX_PHASES + 1]; size_t lds; };
-
-static bool gt_plan(const RdConvDesc* d, GTPlan& pl) {
-    if (!d || d->n_phases < 1 || d->n_phases > RD_MAX_PHASES) return false;
-    if (d->in_stride < 1 || d->in_stride > 2 || d->out_stride < 1 || d->out_stride > 2) return false;
-    if (d->Cin % GT_CK != 0 || d->Cin < 32 || d->Cout < 32 || d->Cout % 8 != 0 || d->ldi % 4 != 0) return false;
-    if ((int64_t)d->N * d->Hi * d->Wi * d->ldi / 2 >= (int64_t)GT_OOB) return false;
-    int64_t rows = 0;
-    for (int i = 0; i < d->n_phases; ++i) {
-        const RdPhase& p = d->phase[i];
-        if (p.n_taps < 1 || p.n_taps > GT_MAXT || p.lh < 1 || p.lw < 1) return false;
-        for (int t = 0; t < p.n_taps; ++t)
-            if (p.widx[t] < 0) return false;
-        rows += (int64_t)d->N * p.lh * p.lw;
+struct GTHost {
+    typedef GTArgs Args;
+    static constexpr const char* name = "gemm_taps_split";
+    static constexpr int CK = GT_CK, MAX_TAPS = GT_MAXT;
+    static bool enabled() { return true; }
+    static int nt(int Cout) { return Cout % 64 == 0 ? 2 : 1; }
+    static size_t lds(int BM, int BN) { return (size_t)BM * 4 * (1 + GT_MAXT) + 8 * BN * 4 + 3 * (size_t)4 * (BM * 16 + GT_UPAD) + 2 * 3 * (size_t)4 * BN * 16; }
+    static int marker(const RdConvDesc& d) {      // taps of the largest phase
+        int taps = 0;
+        for (int i = 0; i < d.n_phases; ++i) taps = taps > d.phase[i].n_taps ? taps : d.phase[i].n_taps;
+        return taps;
     }
-    pl.NT = d->Cout % 64 == 0 ? 2 : 1;
-    if (d->Cout % (pl.NT * 32) != 0) return false;        // (the weight copies read whole column tiles)
-    pl.n_cotiles = d->Cout / (pl.NT * 32);
-    // 256-row tiles when they still give every CU its two workgroups, else 128-row tiles
-    pl.MT = (rows / 256) * pl.n_cotiles >= 2 * (int64_t)num_cus() ? 2 : 1;
-    const int BM = 4 * pl.MT * 32, BN = pl.NT * 32;
-    int tb = 0;
-    for (int i = 0; i < d->n_phases; ++i) {
-        pl.tile_begin[i] = tb;
-        tb += (int)cdiv64((int64_t)d->N * d->phase[i].lh * d->phase[i].lw, BM);
+    template <int MT, int NT>
+    static int launch(const GTArgs& a, int grid, size_t lds, hipStream_t s) {
+        return launch_dyn_lds<gemm_taps_split_kernel<MT, NT>>("gemm_taps_split_kernel", dim3(grid), dim3(256), lds, 80 * 1024, s, a);
     }
-    for (int i = d->n_phases; i <= RD_MAX_PHASES; ++i) pl.tile_begin[i] = tb;
-    pl.tiles = tb;
-    pl.lds = (size_t)BM * 4 * (1 + GT_MAXT) + 8 * BN * 4 + 3 * (size_t)4 * (BM * 16 + GT_UPAD) + 2 * 3 * (size_t)4 * BN * 16;
-    return pl.lds <= 80 * 1024 - 256;
-}
-
-template <int MT, int NT>
-static int launch_gt(const GTArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = gemm_taps_split_kernel<MT, NT>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("gemm_taps_split_kernel");
-    return RD_OK;
-}
-
-static int gemm_taps_split_supported(const RdConvDesc* d) {
-    GTPlan pl;
-    return gt_plan(d, pl) ? 1 : 0;
-}
-
-static int gemm_taps_split_stat_tiles(const RdConvDesc* d) {
-    GTPlan pl;
-    return gt_plan(d, pl) ? pl.tiles : RD_EINVAL;
-}
-
-static int gemm_taps_split_plan_info(const RdConvDesc* d, int32_t* out) {
-    GTPlan pl;
-    if (!out || !gt_plan(d, pl)) return RD_EINVAL;
-    int taps = 0;
-    for (int i = 0; i < d->n_phases; ++i) taps = taps > d->phase[i].n_taps ? taps : d->phase[i].n_taps;
-    const int v[8] = {pl.MT, pl.NT, 4 * pl.MT * 32, 1, 0, (int)pl.lds, pl.tiles * pl.n_cotiles, taps};
-    for (int i = 0; i < 8; ++i) out[i] = v[i];
-    return RD_OK;
-}
-
-static int launch_gemm_taps_split(const RdConvDesc* d, const float* in, const void* w_split, int64_t piece_elems, float* out, const float* bias, int32_t act,
-                       int32_t act_cols, const float* addend, int32_t ld_add, float* stat_partial, hipStream_t s) {
-    GTArgs a;
-    GTPlan pl;
-    if (!gt_plan(d, pl)) { set_error("gemm_taps_split: descriptor not supported"); return RD_EINVAL; }
-    RD_CHECK_ARG(in && w_split && out, "gemm_taps_split: null argument");
-    RD_CHECK_ARG(reinterpret_cast<uintptr_t>(in) % 16 == 0 && reinterpret_cast<uintptr_t>(w_split) % 16 == 0, "gemm_taps_split: unaligned tensor");
-    int S = 0;
-    for (int i = 0; i < d->n_phases; ++i)
-        for (int t = 0; t < d->phase[i].n_taps; ++t) S = S > d->phase[i].widx[t] + 1 ? S : d->phase[i].widx[t] + 1;
-    RD_CHECK_ARG(piece_elems >= (int64_t)S * d->Cin * d->Cout && piece_elems % 8 == 0, "gemm_taps_split: piece stride %lld too small", (long long)piece_elems);
-    a.d = *d;
-    a.in = in; a.w = static_cast<const unsigned short*>(w_split); a.out = out; a.addend = addend; a.bias = bias; a.stat = stat_partial;
-    a.act = act; a.act_cols = act_cols; a.ld_add = ld_add; a.ldw = d->Cout;
-    a.n_cotiles = pl.n_cotiles;
-    a.wplane = (long long)piece_elems * 2;
-    a.vec4 = d->Cout % 4 == 0 && d->ldo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && act_cols % 4 == 0 &&
-             (!addend || (ld_add % 4 == 0 && reinterpret_cast<uintptr_t>(addend) % 16 == 0)) && (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0);
-    for (int i = 0; i <= RD_MAX_PHASES; ++i) a.tile_begin[i] = pl.tile_begin[i];
-    const int grid = pl.tiles * pl.n_cotiles;
-    if (pl.MT == 2 && pl.NT == 2) return launch_gt<2, 2>(a, grid, pl.lds, s);
-    if (pl.MT == 1 && pl.NT == 2) return launch_gt<1, 2>(a, grid, pl.lds, s);
-    if (pl.MT == 2 && pl.NT == 1) return launch_gt<2, 1>(a, grid, pl.lds, s);
-    return launch_gt<1, 1>(a, grid, pl.lds, s);
-}
+};
 
 }  // namespace rd
 using namespace rd;
 
-extern "C" int rd_gemm_taps_split_supported(const RdConvDesc* d) { return gemm_taps_split_supported(d); }
-extern "C" int rd_gemm_taps_split_stat_tiles(const RdConvDesc* d) { return gemm_taps_split_stat_tiles(d); }
-extern "C" int rd_gemm_taps_split_plan_info(const RdConvDesc* d, int32_t* out) { return gemm_taps_split_plan_info(d, out); }
+extern "C" int rd_gemm_taps_split_supported(const RdConvDesc* d) { return row_gemm_supported<GTHost>(d); }
+extern "C" int rd_gemm_taps_split_stat_tiles(const RdConvDesc* d) { return row_gemm_stat_tiles<GTHost>(d); }
+extern "C" int rd_gemm_taps_split_plan_info(const RdConvDesc* d, int32_t* out) { return row_gemm_plan_info<GTHost>(d, out); }
 // Where the plan runs this kernel instead of rd_gconv_split[_pre] (kernel gate, profiles/r07_taps_split_gate.txt, b = 16 450x800): one
 // 4-tap phase at input stride 2 -- the input gradient of a k = 2 transposed convolution -- measured x1.15 / x1.17 / x1.39 against the
 // plan's pre-split kernel on decoder layers 1-3; the four-phase 1/2/2/4-tap descriptors (deconv3's forward, the encoder's stride-2 3x3
 // input gradients) measured x0.72-1.00 against it, and stay there.
 extern "C" int rd_gemm_taps_split_preferred(const RdConvDesc* d) {
-    return gemm_taps_split_supported(d) && d->n_phases == 1 && d->phase[0].n_taps == 4 && d->in_stride == 2 ? 1 : 0;
+    return row_gemm_supported<GTHost>(d) && d->n_phases == 1 && d->phase[0].n_taps == 4 && d->in_stride == 2 ? 1 : 0;
 }
 extern "C" int rd_gemm_taps_split(const RdConvDesc* d, const float* in, const void* w_split, int64_t piece_elems, float* out, const float* bias,
                                   int32_t act, int32_t act_cols, const float* addend, int32_t ld_add, float* stat_partial, void* stream) {
-    return launch_gemm_taps_split(d, in, w_split, piece_elems, out, bias, act, act_cols, addend, ld_add, stat_partial,
-                                  static_cast<hipStream_t>(stream));
+    return row_gemm_launch<GTHost>(d, in, w_split, piece_elems, out, bias, act, act_cols, addend, ld_add, stat_partial, static_cast<hipStream_t>(stream));
 }

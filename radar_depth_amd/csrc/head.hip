@@ -3,12 +3,9 @@
 // All HBM-streaming kernels (one channel out); no matrix cores.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
-
-int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, float* grad_oihw, int S, int Cin, int Cout,
-                       int O, int I, int co_off, int accumulate, hipStream_t s);
 
 // pixel index -> (image, row, column); 32-bit divisions whenever the tensor has fewer than 2^31 pixels (a 64-bit division is
 // ~100 instructions, three of them per pixel were a large part of these streaming kernels)

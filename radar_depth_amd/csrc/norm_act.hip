@@ -2,7 +2,7 @@
 // as HBM-streaming NHWC kernels (float4 over channels, per-channel coefficients).
 // Replaces nn.BatchNorm2d / ReLU / LeakyReLU / `out += identity` / MaxPool2d(3,2,1) and their backward
 // (model/models.py:96-112,203-208,633-650).
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
 

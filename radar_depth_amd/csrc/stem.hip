@@ -5,12 +5,10 @@
 //   wgrad   : [K] x [pixels] x [Cout] with the pixel walk split over the four waves, slabs reduced like wgrad.hip.
 //   dgrad   : only the stage-2 dense-depth input channel needs one (stage-1 output is not detached).
 // Weights use the packed layout [49][Cin][Cout] (rd_pack_weights), i.e. k = (kh*7+kw)*Cin + ci.
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
-
-int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, float* grad_oihw, int S, int Cin, int Cout,
-                       int O, int I, int co_off, int accumulate, hipStream_t s);
 
 struct StemArgs {
     const float* plane[4];
@@ -569,17 +567,11 @@ static int stem_fwd_impl(int io16, const float* const* planes, const int64_t* st
     const int Kq = Kp + 4;
     const size_t lds = ((size_t)((Kq + 3) & ~3) + (size_t)Kq * BN + (size_t)Cin * 21 * ST_PW + (size_t)8 * BN) * 4;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static std::atomic<unsigned long long> attr{0}, attr1{0}, attr4{0};
-    RD_SET_ATTR_ONCE(attr, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    RD_SET_ATTR_ONCE(attr1, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     RD_CHECK_ARG(Cin <= 3 || NT == 2, "stem_fwd: the four-plane stem has 64 output channels (Cout=%d)", Cout);
-    if (Cin == 4) {
-        RD_SET_ATTR_ONCE(attr4, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_fwd_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        hipLaunchKernelGGL((stem_fwd_kernel<2, 4>), dim3(grid), dim3(256), lds, s, a);
-    } else if (NT == 2) hipLaunchKernelGGL(stem_fwd_kernel<2>, dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(stem_fwd_kernel<1>, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("stem_fwd_kernel");
-    return RD_OK;
+    // (the four-plane form is named last: kernels are emitted in the order the host code first names them)
+    if (Cin != 4 && NT == 2) return launch_dyn_lds<stem_fwd_kernel<2>>("stem_fwd_kernel", dim3(grid), dim3(256), lds, 128 * 1024, s, a);
+    if (Cin != 4) return launch_dyn_lds<stem_fwd_kernel<1>>("stem_fwd_kernel", dim3(grid), dim3(256), lds, 128 * 1024, s, a);
+    return launch_dyn_lds<stem_fwd_kernel<2, 4>>("stem_fwd_kernel", dim3(grid), dim3(256), lds, 128 * 1024, s, a);
 }
 
 extern "C" int rd_stem_fwd(const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H, int32_t W,

@@ -6,7 +6,7 @@
 //   A[m = pixel][k] : LDS patch planes [ci][21][69] through a k -> offset table (k = tap * Cin + ci), lane (m = l & 15, k = l >> 4)
 //   B[k][n = co]    : LDS [K][16]
 //   C/D             : lane (co = l & 15) holds pixels 4 (l >> 4) + i of each 16-pixel M-tile: 16 lanes store 64 contiguous bytes
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
 

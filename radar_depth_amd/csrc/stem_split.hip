@@ -17,7 +17,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_host.h"
 
 namespace rd {
 
@@ -318,18 +318,10 @@ extern "C" int rd_stem_fwd_split(const float* const* planes, const int64_t* stri
     RD_CHECK_ARG(Cin <= 3 || NT == 2, "stem_split: the four-plane stem has 64 output channels (Cout=%d)", Cout);
     const size_t lds = ((size_t)2 * 3 * ss_ppl(Cin) + (size_t)3 * 2 * ksteps * NT * 32 * 8) * 2 + (size_t)4 * 2 * NT * 32 * sizeof(float);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto launch = [&](auto k) -> int {
-        static std::atomic<unsigned long long> attr_done{0};      // (one flag per instantiation of this generic lambda)
-        RD_SET_ATTR_ONCE(attr_done, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, a);
-        return RD_OK;
-    };
-    int rc;
-    if (Cin == 4) rc = launch(stem_fwd_split_kernel<2, 4, 0>);
-    else if (NT == 2 && Cin == 3) rc = (dbg & 1) ? launch(stem_fwd_split_kernel<2, 3, 1>) : launch(stem_fwd_split_kernel<2, 3, 0>);
-    else if (NT == 2) rc = Cin == 2 ? launch(stem_fwd_split_kernel<2, 2, 0>) : launch(stem_fwd_split_kernel<2, 1, 0>);
-    else rc = Cin == 3 ? launch(stem_fwd_split_kernel<1, 3, 0>) : Cin == 2 ? launch(stem_fwd_split_kernel<1, 2, 0>) : launch(stem_fwd_split_kernel<1, 1, 0>);
-    if (rc != RD_OK) return rc;
-    RD_CHECK_LAUNCH("stem_fwd_split_kernel");
-    return RD_OK;
+#define RD_SS(NT_, CIN_, DBG_) launch_dyn_lds<stem_fwd_split_kernel<NT_, CIN_, DBG_>>("stem_fwd_split_kernel", dim3(grid), dim3(512), lds, 160 * 1024, s, a)
+    if (Cin == 4) return RD_SS(2, 4, 0);
+    if (NT == 2 && Cin == 3) return (dbg & 1) ? RD_SS(2, 3, 1) : RD_SS(2, 3, 0);
+    if (NT == 2) return Cin == 2 ? RD_SS(2, 2, 0) : RD_SS(2, 1, 0);
+    return Cin == 3 ? RD_SS(1, 3, 0) : Cin == 2 ? RD_SS(1, 2, 0) : RD_SS(1, 1, 0);
+#undef RD_SS
 }

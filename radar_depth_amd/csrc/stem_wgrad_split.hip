@@ -27,12 +27,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
-
-int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, float* grad_oihw, int S, int Cin, int Cout,
-                       int O, int I, int co_off, int accumulate, hipStream_t s);   // wgrad.hip
 
 typedef __bf16 swbf16x8 __attribute__((ext_vector_type(8)));
 typedef short sws16x4 __attribute__((ext_vector_type(4)));
@@ -554,11 +552,6 @@ extern "C" int rd_stem_wgrad_split_supported(int32_t Cin, int32_t Cout) {
     return ((Cin == 3 && Cout == 64) || (Cin >= 1 && Cin <= 2 && Cout == 16) || ((Cin == 4 || Cin == 1) && Cout == 64)) ? 1 : 0;
 }
 
-namespace rd {
-int launch_bn_bwd_coeffs(const float* red_partial, int n_tiles, int C, int which, double count, const float* gamma, const float* invstd,
-                         float* dgamma, float* dbeta, float* coef_ws, hipStream_t s);     // norm_act.hip
-}
-
 static int stem_wgrad_split_impl(int32_t dtype, const float* const* planes, const int64_t* strides, int32_t Cin, int32_t N, int32_t H,
                                  int32_t W, const void* dout, int32_t Cout, float* grad_oihw, float* ws, void* stream, const void* bn_x,
                                  const float* bn_coef, const float* bn_mean) {
@@ -598,10 +591,8 @@ static int stem_wgrad_split_impl(int32_t dtype, const float* const* planes, cons
     const bool bnf = bn_x != nullptr;
 #define RD_SWS(M_, N_, B_, F_)                                                                                       \
     if (MTK == M_ && NT == N_ && b16 == B_ && bnf == F_) {                                                           \
-        static std::atomic<unsigned long long> attr_set{0};       /* (one flag set per instantiation) */             \
-        RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(stem_wgrad_split_kernel<M_, N_, B_, F_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-        hipLaunchKernelGGL((stem_wgrad_split_kernel<M_, N_, B_, F_>), dim3(n_splits), dim3(512), lds, s, a);         \
-        RD_CHECK_LAUNCH("stem_wgrad_split_kernel");                                                                  \
+        const int rc = launch_dyn_lds<stem_wgrad_split_kernel<M_, N_, B_, F_>>("stem_wgrad_split_kernel", dim3(n_splits), dim3(512), lds, lds, s, a); \
+        if (rc != RD_OK) return rc;                                                                                  \
     } else
     RD_SWS(5, 2, false, false) RD_SWS(5, 2, true, false) RD_SWS(2, 1, false, false) RD_SWS(2, 1, true, false) RD_SWS(4, 1, false, false)
     RD_SWS(4, 1, true, false) RD_SWS(5, 2, false, true) RD_SWS(5, 2, true, true) RD_SWS(2, 1, false, true) RD_SWS(2, 1, true, true)

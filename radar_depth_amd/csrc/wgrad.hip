@@ -12,13 +12,12 @@
 // rd_wgrad_reduce sums in a fixed order (deterministic, no atomics) straight into OIHW gradients.
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
+#include <memory>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
 
@@ -593,27 +592,23 @@ static inline bool tile_is_tiled(const struct WgradPlan* tile);
 // ph >= 0: plan one phase of a multi-phase descriptor on its own (compact dout staging); tile: reuse this plan's tile.
 static int plan_wgrad(const RdConvDesc& d_in, WgradPlan& pl, WgradArgs* out, int ph = -1, const WgradPlan* tile = nullptr) {
     RdConvDesc d = d_in;
-    int S_all = 0;
-    for (int i = 0; i < d_in.n_phases; ++i)
-        for (int t = 0; t < d_in.phase[i].n_taps; ++t) S_all = S_all > d_in.phase[i].widx[t] + 1 ? S_all : d_in.phase[i].widx[t] + 1;
     if (ph >= 0) {
         d.n_phases = 1;
         d.phase[0] = d_in.phase[ph];
     }
     const RdPhase& P0 = d.phase[0];
-    int ntaps = 0, S = 0;
+    int ntaps = 0;
     int dh_min = 127, dh_max = -127, dw_min = 127, dw_max = -127;
     for (int i = 0; i < d.n_phases; ++i) {
         const RdPhase& p = d.phase[i];
         RD_CHECK_ARG(p.lh == P0.lh && p.lw == P0.lw, "wgrad: phases must share one logical grid");
         ntaps += p.n_taps;
-        for (int t = 0; t < p.n_taps; ++t) S = S > p.widx[t] + 1 ? S : p.widx[t] + 1;
         dh_min = dh_min < p.dh_min ? dh_min : p.dh_min;
         dh_max = dh_max > p.dh_max ? dh_max : p.dh_max;
         dw_min = dw_min < p.dw_min ? dw_min : p.dw_min;
         dw_max = dw_max > p.dw_max ? dw_max : p.dw_max;
     }
-    S = S_all;
+    const int S = weight_slabs(d_in);      // (of the whole descriptor, also when one phase is planned on its own)
     // rectangular stencil in row-major tap order -> the immediate-offset kernel, whose patch pitch is fixed at WG_PITCH
     const int rw = dw_max - dw_min + 1;
     // (a single-phase 2x2 stencil: the weight gradient of a k = 2 transposed convolution, read as its adjoint stride-2 convolution)
@@ -762,22 +757,12 @@ static inline bool tile_is_tiled(const WgradPlan* tile) { return tile != nullptr
 
 template <int RH, int RW>
 static int launch_strip(const WgradPlan& pl, const WgradArgs& a, int grid, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = wgrad_strip_kernel<RH, RW>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), pl.lds, s, a, pl.sa);
-    RD_CHECK_LAUNCH("wgrad_strip_kernel");
-    return RD_OK;
+    return launch_dyn_lds<wgrad_strip_kernel<RH, RW>>("wgrad_strip_kernel", dim3(grid), dim3(256), pl.lds, 160 * 1024, s, a, pl.sa);
 }
 
 template <int TG, int MF, bool LA, bool SHB, int PITCH = 0, int RW = 3>
 static int launch_wgrad(const WgradArgs& a, int grid, size_t lds, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = wgrad_kernel<TG, MF, LA, SHB, PITCH, RW>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("wgrad_kernel");
-    return RD_OK;
+    return launch_dyn_lds<wgrad_kernel<TG, MF, LA, SHB, PITCH, RW>>("wgrad_kernel", dim3(grid), dim3(256), lds, 160 * 1024, s, a);
 }
 
 // UpProj forward form (4 output phases of a 5x5 stencil on the low-res input): one launch per phase, each a rectangular
@@ -795,18 +780,12 @@ static int plan_any_uncached(const RdConvDesc& d, WgradPlan& pl);
 // plans are a pure function of the descriptor: cached (the tile search would otherwise run on every launch of every step)
 static int plan_any(const RdConvDesc& d, WgradPlan& pl) {
     RD_CHECK_WGRAD_STRIDES(d, "wgrad");
-    static std::mutex mu;
-    static std::unordered_map<std::string, WgradPlan> cache;
-    std::string key(reinterpret_cast<const char*>(&d), sizeof(RdConvDesc));
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(key);
-        if (it != cache.end()) { pl = it->second; return RD_OK; }
-    }
+    static PlanCache<WgradPlan> cache;
+    std::string key = plan_key(d);
+    if (cache.find(key, pl)) return RD_OK;
     const int rc = plan_any_uncached(d, pl);
     if (rc != RD_OK) return rc;
-    std::lock_guard<std::mutex> lk(mu);
-    cache.emplace(std::move(key), pl);
+    cache.insert(std::move(key), pl);
     return RD_OK;
 }
 static int plan_any_uncached(const RdConvDesc& d, WgradPlan& pl) {
@@ -893,17 +872,13 @@ extern "C" int rd_wgrad(const RdConvDesc* d, const float* in, const float* dout,
     if (pl.w16) return launch_wgrad16(*d, in, dout, slabs, s);
     if (pl.w1x1) return launch_wgrad1x1(*d, in, dout, slabs, s);
     // the launch records (plan + kernel arguments minus the tensor pointers) are cached per descriptor like the plans
+    // (entries are shared pointers: a lookup copies a pointer, not the records)
     struct Launch { WgradPlan pl; WgradArgs a; };
-    static std::mutex mu;
-    static std::unordered_map<std::string, std::vector<Launch>> cache;
-    const std::string key(reinterpret_cast<const char*>(d), sizeof(RdConvDesc));
-    const std::vector<Launch>* recs = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = cache.find(key);
-        if (it != cache.end()) recs = &it->second;      // (references into an unordered_map stay valid across inserts)
-    }
-    if (!recs) {
+    typedef std::shared_ptr<const std::vector<Launch>> Records;
+    static PlanCache<Records> cache;
+    std::string key = plan_key(*d);
+    Records recs;
+    if (!cache.find(key, recs)) {
         std::vector<Launch> v;
         if (pl.per_phase) {
             const WgradPlan pl0 = pl;
@@ -920,8 +895,8 @@ extern "C" int rd_wgrad(const RdConvDesc* d, const float* in, const float* dout,
             L.pl.per_phase = 0;
             v.push_back(L);
         }
-        std::lock_guard<std::mutex> lk(mu);
-        recs = &cache.emplace(key, std::move(v)).first->second;
+        recs = std::make_shared<const std::vector<Launch>>(std::move(v));
+        cache.insert(std::move(key), recs);
     }
     if (pl.per_phase) {
         for (const Launch& L : *recs) {
@@ -972,8 +947,6 @@ extern "C" int rd_wgrad_reduce(const RdConvDesc* d, const float* slabs, float* g
 }
 
 // ---- batched reductions (one backward segment's rd_wgrad_reduce / rd_wgrad_bf16_reduce calls as two launches)
-namespace rd { bool wgrad_bf16_reduce_shape(const RdConvDesc* d, int* slab_splits, int* S); }
-
 extern "C" int rd_wgrad_reduce_job(const RdConvDesc* d, int32_t bf16_kernel, const float* slabs, float* grad_oihw, int32_t O, int32_t I,
                                    int32_t KH, int32_t KW, int32_t co_off, int32_t accumulate, RdReduceJob* job) {
     RD_CHECK_ARG(d && slabs && grad_oihw && job, "wgrad_reduce_job: null argument");

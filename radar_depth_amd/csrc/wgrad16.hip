@@ -11,7 +11,7 @@
 //     two-stage slab reduction (rd_wgrad_reduce) like every other weight gradient.
 #include <hip/hip_runtime.h>
 
-#include "common.h"
+#include "conv_internal.h"
 
 namespace rd {
 

@@ -18,7 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
 
@@ -194,12 +195,7 @@ void wgrad1x1_splits(const RdConvDesc& d, int& n_splits, long long& pix_per_spli
 template <int TI, int TO>
 static int launch_w1(const Wgrad1x1Args& a, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * (2 * TI * 32 + 2 * TO * 32) * W1_PC * sizeof(float);
-    static std::atomic<unsigned long long> attr{0};
-    auto k = wgrad1x1_kernel<TI, TO>;
-    RD_SET_ATTR_ONCE(attr, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(a.n_cib * a.n_cob * a.n_splits), dim3(256), lds, s, a);
-    RD_CHECK_LAUNCH("wgrad1x1_kernel");
-    return RD_OK;
+    return launch_dyn_lds<wgrad1x1_kernel<TI, TO>>("wgrad1x1_kernel", dim3(a.n_cib * a.n_cob * a.n_splits), dim3(256), lds, lds, s, a);
 }
 
 int launch_wgrad1x1(const RdConvDesc& d, const float* x, const float* dout, float* slabs, hipStream_t s) {

@@ -25,16 +25,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
-#include <unordered_map>
-
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
-
-int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, float* grad_oihw, int S, int Cin, int Cout,
-                       int O, int I, int co_off, int accumulate, hipStream_t s);   // wgrad.hip
 
 typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
@@ -342,7 +336,6 @@ static bool wgrad_bf16_plan(const RdConvDesc* d, WgradBfPlan& pl) {
     const int IS = d->in_stride;
     pl.lh = d->phase[0].lh; pl.lw = d->phase[0].lw;
     pl.n_pass = 0;
-    int S = 0;
     for (int i = 0; i < d->n_phases; ++i) {
         const RdPhase& p = d->phase[i];
         if (p.lh != pl.lh || p.lw != pl.lw || p.n_taps < 1 || p.n_taps > RD_MAX_TAPS) return false;
@@ -361,10 +354,10 @@ static bool wgrad_bf16_plan(const RdConvDesc* d, WgradBfPlan& pl) {
             int& slot = pl.slab_of_tap[ps][(sh + 1) * 3 + (sw + 1)];
             if (slot >= 0) return false;                                         // two taps on the same shift
             slot = p.widx[t];
-            S = S > p.widx[t] + 1 ? S : p.widx[t] + 1;
         }
     }
     // every slab must be produced exactly once (the reduction reads all S of every split)
+    const int S = weight_slabs(*d);
     if (S < 1 || S > 25) return false;
     int seen[25] = {0};
     for (int ps = 0; ps < pl.n_pass; ++ps)
@@ -397,13 +390,9 @@ static bool wgrad_bf16_plan(const RdConvDesc* d, WgradBfPlan& pl) {
 
 using namespace rd;
 
-static unsigned long long* g_wb_trace = nullptr;
+static TraceBuf<32> g_wb_trace;
 // diagnostics: stamps of the last traced launch (32 slots per workgroup: count, cycle-counter values)
-extern "C" int rd_wgrad_bf16_trace_read(unsigned long long* host, int n_wg) {
-    if (!g_wb_trace) return RD_EINVAL;
-    RD_CHECK_HIP(hipMemcpy(host, g_wb_trace, (size_t)n_wg * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return RD_OK;
-}
+extern "C" int rd_wgrad_bf16_trace_read(unsigned long long* host, int n_wg) { return g_wb_trace.read(host, n_wg); }
 
 extern "C" int rd_wgrad_bf16_supported(const RdConvDesc* d) {
     WgradBfPlan pl;
@@ -451,8 +440,8 @@ static int wgrad_bf16_impl(bool io16, const RdConvDesc* d, const void* in, const
         static const char* tr = getenv("RD_WGRAD_BF16_TRACE");
         if (tr && atoi(tr)) {
             a.trace_loader = atoi(tr) == 2;
-            if (!g_wb_trace) RD_CHECK_HIP(hipMalloc(&g_wb_trace, (size_t)65536 * 32 * sizeof(unsigned long long)));
-            a.trace = g_wb_trace;
+            const int rc = g_wb_trace.get(a.trace);
+            if (rc != RD_OK) return rc;
         }
     }
     bool full = true;
@@ -463,14 +452,8 @@ static int wgrad_bf16_impl(bool io16, const RdConvDesc* d, const void* in, const
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define RD_WB(FULL_, NK_) RD_WB2(FULL_, NK_, false) RD_WB2(FULL_, NK_, true)
 #define RD_WB2(FULL_, NK_, IO_)                                                                                                 \
-    if (full == FULL_ && nk == NK_ && io16 == IO_) {                                                                            \
-        static std::atomic<unsigned long long> attr_set{0};                                                                                           \
-        auto k = wgrad_bf16_kernel<FULL_, NK_, IO_>;                                                                            \
-        RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                                                                                                                       \
-        hipLaunchKernelGGL(k, grid, dim3(512), pl.lds_bytes, st, a);                                                            \
-        RD_CHECK_LAUNCH("wgrad_bf16_kernel");                                                                                   \
-        return RD_OK;                                                                                                           \
-    }
+    if (full == FULL_ && nk == NK_ && io16 == IO_)                                                                              \
+        return launch_dyn_lds<wgrad_bf16_kernel<FULL_, NK_, IO_>>("wgrad_bf16_kernel", grid, dim3(512), pl.lds_bytes, 160 * 1024, st, a);
     RD_WB(true, 1) RD_WB(true, 2) RD_WB(true, 4) RD_WB(false, 1) RD_WB(false, 2) RD_WB(false, 4)
 #undef RD_WB
 #undef RD_WB2

@@ -23,16 +23,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
-#include <string>
-#include <unordered_map>
-
-#include "common.h"
+#include "conv_host.h"
+#include "conv_internal.h"
 
 namespace rd {
-
-int launch_slab_reduce(const float* slabs, int n_splits, int64_t E, float* tmp, float* grad_oihw, int S, int Cin, int Cout,
-                       int O, int I, int co_off, int accumulate, hipStream_t s);   // wgrad.hip
 
 typedef __bf16 wsbf16x8 __attribute__((ext_vector_type(8)));
 typedef short wss16x4 __attribute__((ext_vector_type(4)));
@@ -412,8 +406,7 @@ static WsPlan ws_plan(const RdConvDesc& d) {
     pl.total_tiles = d.N * pl.tiles_h * pl.tiles_w;
     pl.n_cib = cdiv(d.Cin, 64);
     pl.n_cob = cdiv(d.Cout, 64);
-    for (int i = 0; i < d.n_phases; ++i)
-        for (int t = 0; t < d.phase[i].n_taps; ++t) pl.S = pl.S > d.phase[i].widx[t] + 1 ? pl.S : d.phase[i].widx[t] + 1;
+    pl.S = weight_slabs(d);
     // one workgroup per CU: about num_cus workgroups in all, at least four tiles per split (the first tile's staging is exposed)
     static const char* wpc = getenv("RD_WGRAD_SPLIT_WG_PER_CU");      // diagnostics
     int ns = (wpc ? atoi(wpc) : 1) * num_cus() / (pl.n_cib * pl.n_cob);
@@ -428,12 +421,7 @@ static WsPlan ws_plan(const RdConvDesc& d) {
 
 template <int TR, int TC, typename G, bool PRE>
 static int launch_ws(const WsArgs& a, int grid, hipStream_t s) {
-    static std::atomic<unsigned long long> attr_set{0};
-    auto k = wgrad_split_kernel<TR, TC, G, PRE>;
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), 2 * (PRE ? G::BUF_P : G::BUF), s, a);
-    RD_CHECK_LAUNCH("wgrad_split_kernel");
-    return RD_OK;
+    return launch_dyn_lds<wgrad_split_kernel<TR, TC, G, PRE>>("wgrad_split_kernel", dim3(grid), dim3(512), 2 * (PRE ? G::BUF_P : G::BUF), 160 * 1024, s, a);
 }
 
 }  // namespace rd

@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_host.h"
 
 namespace rd {
 
@@ -541,18 +541,9 @@ static int wino_launch(const float* in, int32_t N, int32_t H, int32_t W, int32_t
     a.dbg = dbg;
     const int grid = N * a.bh * a.bw * a.n_cot;
     const size_t lds = 2 * (size_t)WN_BUF;
-    static std::atomic<unsigned long long> attr_set{0};
-    if (dbg & 1) {
-        static std::atomic<unsigned long long> attr_dbg{0};
-        RD_SET_ATTR_ONCE(attr_dbg, hipFuncSetAttribute(reinterpret_cast<const void*>(wino_split_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(wino_split_kernel<true>, dim3(grid), dim3(512), lds, static_cast<hipStream_t>(stream), a);
-        RD_CHECK_LAUNCH("wino_split_kernel");
-        return RD_OK;
-    }
-    RD_SET_ATTR_ONCE(attr_set, hipFuncSetAttribute(reinterpret_cast<const void*>(wino_split_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(wino_split_kernel<false>, dim3(grid), dim3(512), lds, static_cast<hipStream_t>(stream), a);
-    RD_CHECK_LAUNCH("wino_split_kernel");
-    return RD_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (dbg & 1) return launch_dyn_lds<wino_split_kernel<true>>("wino_split_kernel", dim3(grid), dim3(512), lds, 160 * 1024, s, a);
+    return launch_dyn_lds<wino_split_kernel<false>>("wino_split_kernel", dim3(grid), dim3(512), lds, 160 * 1024, s, a);
 }
 
 extern "C" int rd_wino_conv3x3(const float* in, int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t ldi, const void* u_packed, float* out,

@@ -417,5 +417,6 @@ def checks_precede_launches(source, function):
     at = source.index(" " + function + "(")
     body = source[at:source.index("\n}\n", at)]
     checks = [i for i in range(len(body)) if body.startswith("RD_CHECK_ARG(", i)]
-    launch = body.find("hipLaunchKernelGGL")
-    return bool(checks) and launch > 0 and max(checks) < launch
+    # (a launch: hipLaunchKernelGGL, or the shared prologue of the kernels with > 64 KB of dynamic LDS, csrc/conv_host.h)
+    launches = [i for i in (body.find("hipLaunchKernelGGL"), body.find("launch_dyn_lds<")) if i > 0]
+    return bool(checks) and bool(launches) and max(checks) < min(launches)

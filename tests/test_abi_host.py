@@ -242,3 +242,108 @@ def test_no_kernel_spills_vector_registers():
                 bad.append((f, name, r.get("VGPRs Spill", 0), r.get("ScratchSize [bytes/lane]", 0)))
     assert n > 150, "resource reports missing (%d kernels seen): rebuild with python -m radar_depth_amd.build --force" % n
     assert not bad, bad
+
+
+# ---- the shared host layer of the convolution files (csrc/conv_host.h): cache key, plan-all switches, error texts, source lint
+def _info(fn, d, n):
+    out = (C.c_int32 * n)()
+    assert fn(C.byref(d), out) == 0, fn.__name__
+    return list(out)
+
+
+def test_stale_tile_begin_does_not_make_a_second_plan(L):
+    """The tile_begin fields are filled by the library: a caller's stale values in them must reach the plan already cached for the
+    descriptor -- same state, same answers -- not plan it a second time."""
+    from radar_depth_amd import convdesc as cd
+    d = cd.conv_fwd(3, 23, 37, 64, 128, 3, 1, 1)            # (a shape no other test plans)
+    assert L.rd_gconv_plan_state(C.byref(d), 1) == 0
+    queries = ((L.rd_gconv_plan_info, 10), (L.rd_gconv_bf16_plan_info, 8), (L.rd_gconv_split_plan_info, 8))
+    want = [_info(fn, d, n) for fn, n in queries]
+    tiles = L.rd_gconv_stat_tiles(C.byref(d))
+    assert tiles > 0 and L.rd_gconv_plan_state(C.byref(d), 1) == 2
+    e = cd.RdConvDesc()
+    C.memmove(C.byref(e), C.byref(d), C.sizeof(d))
+    for i in range(4):
+        e.phase[i].tile_begin = 1000 + 17 * i
+    assert bytes(e) != bytes(d)
+    assert L.rd_gconv_plan_state(C.byref(e), 1) == 2
+    assert [_info(fn, e, n) for fn, n in queries] == want and L.rd_gconv_stat_tiles(C.byref(e)) == tiles
+
+
+def test_plan_all_switches_return_the_previous_value_and_drop_stale_plans(L):
+    """rd_gconv_split_plan_all / rd_gconv_bf16p_plan_all: each call returns the setting it replaces, and a descriptor served only
+    under "all" is answered 0 / 1 / 0 across the toggles -- the answer cached under one setting does not outlive it."""
+    from radar_depth_amd import convdesc as cd
+    d = cd.conv_fwd(2, 19, 27, 32, 32, 3, 1, 1)             # 3x3 with 32 channels a side: left to rd_gconv unless "all"
+    first = L.rd_gconv_split_plan_all(0)
+    try:
+        assert L.rd_gconv_split_supported(C.byref(d)) == 0
+        assert L.rd_gconv_split_plan_all(1) == 0 and L.rd_gconv_split_supported(C.byref(d)) == 1
+        assert L.rd_gconv_split_plan_all(1) == 1 and L.rd_gconv_split_supported(C.byref(d)) == 1
+        assert L.rd_gconv_split_plan_all(0) == 1 and L.rd_gconv_split_supported(C.byref(d)) == 0
+    finally:
+        L.rd_gconv_split_plan_all(first)
+
+    def persistent(desc):           # (+ 2000 in the chunk slot marks the persistent kernel)
+        out = (C.c_int32 * 8)()
+        assert L.rd_gconv_bf16_plan_info_t(1, C.byref(desc), out) == 0
+        return (1 if out[2] >= 2000 else 0), out[0]
+    p = cd.conv_fwd(2, 15, 25, 64, 64, 3, 1, 1)             # small-spatial 3x3: 128-pixel tiles, which the planner rule leaves out
+    first = L.rd_gconv_bf16p_plan_all(0)
+    try:
+        assert persistent(p)[0] == 0
+        assert L.rd_gconv_bf16p_plan_all(1) == 0 and persistent(p) == (1, 1)
+        assert L.rd_gconv_bf16p_plan_all(0) == 1 and persistent(p)[0] == 0
+    finally:
+        L.rd_gconv_bf16p_plan_all(first)
+
+
+def test_descriptor_error_texts(L):
+    """rd_last_error() of the descriptor checks, byte for byte, through the three entry points that validate with messages."""
+    from radar_depth_amd import convdesc as cd
+
+    def bad(edit, Cin=32):
+        d = cd.conv_fwd(2, 11, 17, Cin, 32, 3, 1, 1)
+        edit(d)
+        return d
+
+    def set_n_phases(d): d.n_phases = 0
+    def set_tap(d): d.phase[0].dh[4] = 5
+    def set_empty(d): d.phase[0].lw = 0
+    cases = [(bad(set_n_phases), "n_phases=0"), (bad(set_tap), "tap 4 of phase 0 outside its declared range"),
+             (bad(lambda d: None, Cin=24), "Cin=24 must be a multiple of 16, ldi=24 of 4"), (bad(set_empty), "empty phase 0")]
+    out = (C.c_int32 * 10)()
+    for d, text in cases:
+        assert L.rd_gconv_plan_info(C.byref(d), out) == -1 and L.rd_last_error() == b"gconv: " + text.encode()
+        assert L.rd_gconv_bf16_plan_info(C.byref(d), out) == -1 and L.rd_last_error() == b"gconv_bf16: " + text.encode()
+        assert L.rd_gconv_tune_pin(C.byref(d), 1, None) == -1 and L.rd_last_error() == b"gconv: " + text.encode()
+
+
+def test_conv_host_code_lives_in_one_place():
+    """Source lint over csrc/*.hip: the dynamic-LDS attribute is set by launch_dyn_lds alone (occ_cfg of gconv.hip, a diagnostic,
+    sets it without the per-device bit on purpose), plan caches are PlanCache (no string-keyed map of a file's own), and no file
+    declares a function that another .hip defines -- those declarations live in conv_internal.h."""
+    import glob
+    root = os.path.join(REPO, "radar_depth_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(root, "*.hip")))
+    assert len(files) > 25
+    proto = re.compile(r"^(?:namespace\s+\w+\s*\{\s*)?(?!static\b|extern\b|template\b|typedef\b|using\b|return\b|namespace\b)[A-Za-z_][\w:<>\*& ]*?\b(\w+)\([^;{}]*\)\s*;", re.M)
+    offenders = []
+    for f in files:
+        name, text = os.path.basename(f), open(f).read()
+        code = re.sub(r"//[^\n]*", "", text)
+        attr = [m.start() for m in re.finditer("hipFuncAttributeMaxDynamicSharedMemorySize", code)]
+        if name == "gconv.hip":
+            assert len(attr) == 1 and "occ_cfg" in code[code.rfind("template", 0, attr[0]):attr[0]]
+        elif attr:
+            offenders.append((name, "sets the dynamic-LDS attribute itself"))
+        # (the slot table of gconv_split.hip is a string-keyed map of device pointers, not a plan cache)
+        if len(re.findall(r"unordered_map<std::string", code)) > (1 if name == "gconv_split.hip" else 0):
+            offenders.append((name, "string-keyed map"))
+        for m in proto.finditer(code):
+            if not re.search(r"^[A-Za-z_][\w:<>\*& ]*\b%s\([^;{}]*\)\s*\{" % re.escape(m.group(1)), code, re.M):
+                offenders.append((name, "declares %s, defined elsewhere" % m.group(1)))
+    assert offenders == []
+    internal = open(os.path.join(root, "conv_internal.h")).read()
+    for fn in ("launch_slab_reduce", "launch_bn_bwd_coeffs", "wgrad_bf16_reduce_shape", "launch_conv16", "gemm1_split_supported"):
+        assert len(re.findall(r"\b%s\(" % fn, internal)) == 1
