@@ -890,6 +890,68 @@ int rd_render_rows(const float* rgb, int64_t rgb_stride, const float* const* pla
                    int32_t B, int32_t H, int32_t W, const double* range, void* workspace, const uint8_t* table, uint8_t* out,
                    int64_t frame_stride, int64_t row_pitch, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The KITTI depth devkit's evaluation on the device (csrc/kitti_eval.hip): the reference's misc/devkit/cpp -- readDepthMap,
+ * writeDepthMap, interpolateBackground, depthError, errorImage(D_gt, true), statMean / statMin / statMax -- with its arithmetic and
+ * its quirks.  A depth plane is float32 [H][W], contiguous; a pixel is valid when d >= 0 (NaN is invalid, 0.0 and -0.0 are valid) and
+ * invalid pixels hold -1.  Every entry point takes B frames, frame b `*_stride` ELEMENTS after frame b-1 (inputs[:, 3:4] of a
+ * [B,4,H,W] tensor: 4*H*W).  zero_invalid != 0: a ground-truth pixel is valid when gt > 0 (this project's targets hold 0 for "no
+ * measurement"); gt is otherwise read as it is.  No entry point synchronises with the host, allocates, or uses a floating-point
+ * atomic: two calls give the same bits.
+ *
+ * decode       uint16 0 -> -1.0f, any other v -> (float)v / 256.
+ * encode       a valid d -> (uint16) trunc(max((double)d * 256.0, 1.0)), an invalid one -> 0.  A product above 65535 is undefined
+ *              behaviour in the reference's cast; here it SATURATES at 65535 (+inf too).
+ * interpolate  Rows: an invalid pixel with the nearest originally valid pixels L to its left and R to its right in its row becomes
+ *              R < L ? R : L, with one of them that one, with neither it keeps its value.  Columns: the rows above the first row that
+ *              holds a valid pixel copy that row as filled, the rows below the last such row copy that one; an all-invalid row BETWEEN
+ *              valid rows stays as it is (the reference extrapolates to the top and the bottom only); a frame without a valid pixel is
+ *              unchanged.  out may be `in` itself (same pointer and stride); otherwise the two must not overlap.  Two launches.
+ * errors       out[B][10] doubles: mae, rmse, inverse mae, inverse rmse, log mae, log rmse, scale invariant log, abs relative,
+ *              squared relative, then the number of valid ground-truth pixels.  Per valid pixel, in the reference's types:
+ *              d = |gt - p| (float32), d2 = d * d, di = (float)|1.0 / gt - 1.0 / p| (formed in double), di2 = di * di,
+ *              ld = log((double)gt) - log((double)p), dl = (float)|ld|, dl2 = dl * dl, rel = d / gt, sq = d2 / (gt * gt) (float32,
+ *              IEEE division).  The eight sums and sum(ld) are accumulated in float64 in an order fixed by (H, W) alone; the final
+ *              values are float64: S/n, sqrt(S2/n), ..., silog = sqrt(Sl2/n - (sum(ld)/n)^2) (NaN for a negative argument, as in the
+ *              reference).  n == 0 gives nine NaNs and a count of 0 (the reference throws).  A prediction of -1 or 0 poisons the
+ *              sums with NaN / inf as it does there.  Two launches.
+ * error_image  packed uint8 RGB, row y of frame b at out + b * frame_stride + y * row_pitch (BYTES, no alignment asked), 3*W bytes;
+ *              no other byte is written.  A centre (u, v), 1 <= u <= W-2, 1 <= v <= H-2, with a valid gt has d_err = |p - gt|
+ *              (float32), a = d_err / 3.0, b = 20.0 * d_err / |gt| (double), n_err = (float)(b < a ? b : a) and the colour of the row
+ *              of `table` with lo <= n_err < hi (float32 comparisons), black without one (NaN, n_err >= the last bound).  An output
+ *              pixel takes the colour of the LAST centre in raster order among its up to nine neighbours (itself included) that
+ *              has a valid gt; black if none has.  table: HOST array [10][5] floats lo, hi, r, g, b
+ *              (radar_depth_amd/kitti_log_colormap.json), copied into the kernel arguments.  One launch.
+ * stats_update folds the B rows of `errors` (as `errors` above writes them), in order, into state[9][4] doubles = per metric the sum,
+ *              the minimum, the maximum and the number of frames.  The caller starts the state at {0, 1, 0, 0}: statMin starts
+ *              at 1 and statMax at 0, and a NaN fails both comparisons but poisons the sum.  One launch of one workgroup.
+ * ws: rd_kitti_workspace_bytes(B, H, W) bytes, 8-byte aligned, for interpolate and for errors (calls on one stream may share it).
+ *
+ * Argument checks run before anything reaches the GPU, each with a code of its own:
+ *   RD_EKITTI_NULL     a null pointer
+ *   RD_EKITTI_RANGE    B, H or W outside 1..65535
+ *   RD_EKITTI_STRIDE   a frame stride below H*W
+ *   RD_EKITTI_ALIGN    ws, out of errors, or errors / state of stats_update not 8-byte aligned
+ *   RD_EKITTI_PITCH    row_pitch below 3*W, or frame_stride below H*row_pitch
+ *   RD_EKITTI_OVERLAP  interpolate's out overlaps `in` without being `in` (same pointer, same stride)
+ * rd_kitti_workspace_bytes returns RD_EKITTI_RANGE for sizes the calls reject. */
+#define RD_EKITTI_NULL (-49)
+#define RD_EKITTI_RANGE (-50)
+#define RD_EKITTI_STRIDE (-51)
+#define RD_EKITTI_ALIGN (-52)
+#define RD_EKITTI_PITCH (-53)
+#define RD_EKITTI_OVERLAP (-54)
+int64_t rd_kitti_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int rd_kitti_decode(const uint16_t* in, int64_t in_stride, float* out, int64_t out_stride, int32_t B, int32_t H, int32_t W, void* stream);
+int rd_kitti_encode(const float* in, int64_t in_stride, uint16_t* out, int64_t out_stride, int32_t B, int32_t H, int32_t W, void* stream);
+int rd_kitti_interpolate(const float* in, int64_t in_stride, float* out, int64_t out_stride, int32_t B, int32_t H, int32_t W, void* ws,
+                         void* stream);
+int rd_kitti_errors(const float* gt, int64_t gt_stride, const float* pred, int64_t pred_stride, int32_t B, int32_t H, int32_t W,
+                    int32_t zero_invalid, void* ws, double* out, void* stream);
+int rd_kitti_error_image(const float* gt, int64_t gt_stride, const float* pred, int64_t pred_stride, int32_t B, int32_t H, int32_t W,
+                         int32_t zero_invalid, const float* table, uint8_t* out, int64_t frame_stride, int64_t row_pitch, void* stream);
+int rd_kitti_stats_update(const double* errors, int32_t B, double* state, void* stream);
+
 /* NCHW [N,C,H,W] (channel c0..c0+C of Ctot) <-> NHWC helpers for module-level tests */
 int rd_nchw_to_nhwc(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 int rd_nhwc_to_nchw(const float* src, float* dst, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);

@@ -27,6 +27,9 @@ RD_MDIST_MAX_INTERVALS = 16
 # ... and of the PnP-Depth kernels (csrc/pnp.hip)
 RD_EPNP_NULL, RD_EPNP_RANGE, RD_EPNP_STRIDE, RD_EPNP_ACT, RD_EPNP_DTYPE, RD_EPNP_OVERLAP = -43, -44, -45, -46, -47, -48
 
+# ... and of the KITTI devkit evaluation (csrc/kitti_eval.hip)
+RD_EKITTI_NULL, RD_EKITTI_RANGE, RD_EKITTI_STRIDE, RD_EKITTI_ALIGN, RD_EKITTI_PITCH, RD_EKITTI_OVERLAP = -49, -50, -51, -52, -53, -54
+
 
 class RdPhase(C.Structure):
     _fields_ = [("n_taps", C.c_int32), ("out_off_h", C.c_int32), ("out_off_w", C.c_int32),

@@ -152,6 +152,13 @@ std::string signature(const char* name, R (*)(A...)) {
     X(rd_head_conv_fwd) \
     X(rd_head_conv_fwd_t) \
     X(rd_head_conv_wgrad_t) \
+    X(rd_kitti_decode) \
+    X(rd_kitti_encode) \
+    X(rd_kitti_error_image) \
+    X(rd_kitti_errors) \
+    X(rd_kitti_interpolate) \
+    X(rd_kitti_stats_update) \
+    X(rd_kitti_workspace_bytes) \
     X(rd_l1_total) \
     X(rd_last_error) \
     X(rd_lidar_radar_sparsify) \
